@@ -10,6 +10,12 @@ exchange overlaps batch k+1's insert; two tables alternate); every batch's work 
 the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1..5] [--rows R]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (rows/s, ms_per_step).
+--dump-outputs DIR also writes the result columns of the last timed step as DIR/<name>.npy.
+--full adds everything else to the line: the per-kernel pass and the roofline, ORDER BY ... LIMIT,
+the CPU baseline and its parity check, the other configurations and the scan side.
 
 Multi-GPU: launched by torch.distributed.run, one rank per GPU (backend nccl = RCCL); every rank
 aggregates its own 100M rows (weak scaling), timing = max over ranks, value = all ranks' rows / time.
@@ -38,6 +44,14 @@ def parse():
     p.add_argument("--config", type=int, default=2)
     p.add_argument("--rows", type=int, default=0, help="rows per GPU (default: the config's size)")
     p.add_argument("--copies", type=int, default=0, help="rotating input copies (default: enough to defeat the 256 MiB L3)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: per-kernel times and the roofline, "
+                        "ORDER BY LIMIT, the CPU baseline (--no-cpu-baseline drops it), the other configurations "
+                        "(--extra-configs) and the scan side")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="single GPU: after the timed steps write the last timed step's result columns (group keys and "
+                        "aggregates) as DIR/<name>.npy in float64, rows in ascending order of the written values; "
+                        "above 64 MB in all, a fixed sample of the groups chosen by a hash of their key")
     p.add_argument("--cpu-sample-rows", type=int, default=0)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--capacity-hint", type=int, default=0)
@@ -63,7 +77,117 @@ def parse():
     p.add_argument("--scaling", choices=["weak", "strong"], default=None,
                    help="weak: every GPU aggregates the config's rows; strong: the config's rows are split over "
                         "the GPUs (default: strong for the 1B-row configs 3-5, weak for 1-2)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        p.error("--dump-outputs writes one GPU's result columns: use --gpus 1")
+    return args
+
+
+DUMP_CAP_BYTES = 60_000_000  # all DIR/*.npy together stay under 64 MB, headers included
+
+
+def _mix64(v):
+    """A fixed 64-bit mix of an int64 tensor (wrapping multiplies, splitmix64's constants)."""
+    v = v * -7046029254386353131
+    v = v ^ (v >> 31)
+    v = v * -4658895280553007687
+    return v ^ (v >> 29)
+
+
+def _string_features(torch, c, n):
+    """Per row of a string column, on its device: byte length, sum of bytes, and sum of bytes
+    weighted by their 1-based position in the string (int64, wrapping)."""
+    offs = c.offsets[:n + 1]
+    total = int(offs[n].item()) if n else 0
+    b = c.data[:total].long()
+    z = torch.zeros(1, dtype=torch.int64, device=b.device)
+    p1 = torch.cat([z, torch.cumsum(b, 0)])
+    p2 = torch.cat([z, torch.cumsum(b * torch.arange(total, device=b.device), 0)])
+    s, e = offs[:-1], offs[1:]
+    s1 = p1[e] - p1[s]
+    return e - s, s1, (p2[e] - p2[s]) - (s - 1) * s1
+
+
+def _bits(bitmap, idx):
+    return (bitmap[idx >> 3].long() >> (idx & 7)) & 1
+
+
+def _column_arrays(torch, name, c, n, idx, feats=None):
+    """[(name, float64 host array)] of rows idx (int64 tensor on c's device) of the first n rows of
+    device column c.  Fixed-width values are converted (Decimal128: the unscaled integer), a string
+    gives its three _string_features, a nullable column a `_valid` array and 0 at its nulls."""
+    from databend_amd import abi
+    t = c.dtype.type_id
+    if t == abi.STRING:
+        ln, s1, s2 = feats if feats is not None else _string_features(torch, c, n)
+        arrs = [(name + "_len", ln[idx]), (name + "_bytesum", s1[idx]), (name + "_wsum", s2[idx])]
+        arrs = [(k, v.cpu().numpy().astype(np.float64)) for k, v in arrs]
+    elif t == abi.BOOLEAN:
+        arrs = [(name, _bits(c.data, idx).cpu().numpy().astype(np.float64))]
+    else:
+        w = c.dtype.width
+        raw = c.data[:n * w].view(n, w)[idx].cpu().numpy()
+        if t == abi.DECIMAL128:
+            lo = raw[:, :8].copy().view(np.uint64).reshape(-1)
+            hi = raw[:, 8:].copy().view(np.int64).reshape(-1)
+            slo = lo.view(np.int64)  # a value that fits 64 bits converts without the 2^64 round trip
+            v = np.where(hi == (slo >> 63), slo.astype(np.float64), hi.astype(np.float64) * 2.0**64 + lo.astype(np.float64))
+        else:
+            v = np.ascontiguousarray(raw).view(c.dtype.np_dtype).reshape(-1).astype(np.float64)
+        arrs = [(name, v)]
+    if c.dtype.nullable and c.validity is not None:
+        valid = _bits(c.validity, idx).cpu().numpy().astype(np.float64)
+        arrs = [(k, np.where(valid > 0, v, 0.0)) for k, v in arrs] + [(name + "_valid", valid)]
+    return arrs
+
+
+def dump_outputs(path, key_names, keys, agg_names, aggs, n, cap_bytes=DUMP_CAP_BYTES):
+    """Write the n result rows held in the device columns keys + aggs as path/<name>.npy (float64)
+    plus n_groups.npy.  The order of a GROUP BY's rows is not part of its result, so the rows are
+    written in ascending order of the written values, key columns first.  If they would exceed
+    cap_bytes, only the groups whose key hashes (_mix64) below a fixed threshold are written: the
+    same groups in every run over the same input, in whatever order the table emitted them."""
+    import torch
+    from databend_amd import abi
+    os.makedirs(path, exist_ok=True)
+    cols = [("key_" + k, c) for k, c in zip(key_names, keys)] + list(zip(agg_names, aggs))
+    n_arrays = sum((3 if c.dtype.type_id == abi.STRING else 1) + (1 if c.dtype.nullable else 0) for _, c in cols)
+    cap_rows = max(1, cap_bytes // (8 * n_arrays))
+    dev = cols[0][1].data.device
+    feats = {}
+    if n <= cap_rows:
+        idx = torch.arange(n, dtype=torch.int64, device=dev)
+    else:
+        # the sample: rows whose first key column hashes into the lowest `thr` of 2^20 buckets
+        thr = max(1, int(0.9 * cap_rows / n * (1 << 20)))
+        k0 = cols[0][1]
+        picked = []
+        if k0.dtype.type_id == abi.STRING:
+            feats[0] = ln, s1, s2 = _string_features(torch, k0, n)
+            h = _mix64(ln ^ _mix64(s1 ^ _mix64(s2)))
+            picked.append(torch.nonzero(((h >> 20) & 0xFFFFF) < thr).reshape(-1))
+        else:
+            w = k0.dtype.width
+            it = {1: torch.int8, 2: torch.int16, 4: torch.int32}.get(w, torch.int64)
+            for lo in range(0, n, 1 << 26):
+                hi = min(n, lo + (1 << 26))
+                if k0.dtype.type_id == abi.BOOLEAN:
+                    v = _bits(k0.data, torch.arange(lo, hi, dtype=torch.int64, device=dev))
+                else:
+                    v = k0.data[lo * w:hi * w].view(it).long()
+                if w == 16:
+                    v = v.view(-1, 2)
+                    v = v[:, 0] ^ _mix64(v[:, 1])
+                h = _mix64(v)
+                picked.append(torch.nonzero(((h >> 20) & 0xFFFFF) < thr).reshape(-1) + lo)
+        idx = torch.cat(picked)
+    arrs = []
+    for j, (name, c) in enumerate(cols):
+        arrs += _column_arrays(torch, name, c, n, idx, feats.get(j))
+    order = np.lexsort([a for _, a in arrs][::-1])[:cap_rows] if arrs and len(idx) else np.zeros(0, np.int64)
+    for name, a in arrs:
+        np.save(os.path.join(path, name + ".npy"), a[order])
+    np.save(os.path.join(path, "n_groups.npy"), np.array([n], dtype=np.float64))
 
 
 def cpu_baseline(cfg, sample_rows, gpu_check=None):
@@ -383,36 +507,8 @@ def main():
     if world > 1:
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
-    # Kernel durations for the roofline: a second pass of the same steps with HIP events recorded
-    # around every launch on the stream it runs on (dbg_prof_enable).  Kept out of the timed pass
-    # above: event records add host and GPU work between launches.
-    ffi.prof_reset()
-    ffi.prof_enable(True)
-    for k in range(args.steps):
-        step(args.warmup + args.steps + k)
-    drain()
-    torch.cuda.synchronize()
-    ffi.prof_enable(False)
-    prof = ffi.prof_read()
 
-    # dominant kernel: the fused filter + GROUP BY insert (HBM-table strategy), or — radix-
-    # partitioned strategy (pp.hip, high cardinality) — the whole step's level passes + LDS
-    # aggregation, whose launches together touch the §8d bytes once
-    partitioned = runner.table.strategy()[0]
-    if partitioned:
-        pp_names = [k for k in prof if k.startswith("pp_") and k != "pp_probe"]
-        ins_ms = sum(prof[k][0] for k in pp_names)
-        ins_n = args.steps
-        kernel_name = "+".join(sorted(pp_names)) + " (one step)"
-    else:
-        ins_ms, ins_n = prof.get("agg_insert", (0.0, 0))
-        kernel_name = "agg_insert"
-        if "part_direct" in prof:  # C3: the sort in the insert, the table stage in the finalize (part.hip)
-            ins_ms += prof["part_direct"][0]
-            kernel_name = "agg_insert+part_direct"
-    avg_ms = ins_ms / max(1, ins_n)
-    # algorithmic bytes of one insert launch (SURVEY.md §8d)
-    keys_h = aggs_h = None
+    # groups and selected rows of the last timed step (N > 1: of this rank's partial of copy 0)
     if world == 1:
         n_groups = runner.n_groups
         kstr = runner.key_string_bytes
@@ -420,7 +516,6 @@ def main():
         runner.insert(0)  # (untimed) this rank's partial of copy 0, for the byte accounting
         n_groups = runner.table.finalize()[0]
         kstr = 0
-        keys_h, aggs_h = None, None
     # selected rows: SUM of COUNT(*) over the partial table of this rank
     sel = None
     ci_star = next((i for i, (f, c) in enumerate(shape.aggs) if f == "count" and c is None), None)
@@ -430,8 +525,7 @@ def main():
         blk = runner.table.merge_result()
         ci = [i for i, (f, c) in enumerate(shape.aggs) if f == "count" and c is None]
         sel = int(sum(blk.columns[ci[0]].values())) if ci else rows
-    alg_bytes = algorithmic_bytes(cfg, runner.inputs[0], rows, sel, n_groups, runner.result_types, kstr)
-    achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+    partitioned = runner.table.strategy()[0]
 
     value = rows * world * args.steps / elapsed
     out = {
@@ -453,12 +547,52 @@ def main():
                    "strategy": "partitioned" if partitioned else "hbm_table",
                    "exchange": (("before_partial" if before_partial else "before_merge") + "/" + args.exchange)
                    if world > 1 and not small else ("replicas+gather" if world > 1 else None)},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                     "kernel": kernel_name, "kernel_avg_ms": avg_ms, "kernel_launches": ins_n,
-                     "algorithmic_bytes_per_launch": alg_bytes},
-        "kernels_ms_per_step": {k: v[0] / args.steps for k, v in prof.items()},
     }
+    if args.dump_outputs and rank == 0:
+        agg_names = [f"agg{i}_{f}" + (f"_{c}" if c else "") for i, (f, c) in enumerate(shape.aggs)]
+        dump_outputs(args.dump_outputs, shape.keys, runner.out_keys, agg_names, runner.out_aggs, n_groups)
+    if not args.full:  # a plain run ends here: the headline figure needs nothing more
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # Kernel durations for the roofline: a second pass of the same steps with HIP events recorded
+    # around every launch on the stream it runs on (dbg_prof_enable).  Kept out of the timed pass
+    # above: event records add host and GPU work between launches.
+    ffi.prof_reset()
+    ffi.prof_enable(True)
+    for k in range(args.steps):
+        step(args.warmup + args.steps + k)
+    drain()
+    torch.cuda.synchronize()
+    ffi.prof_enable(False)
+    prof = ffi.prof_read()
+
+    # dominant kernel: the fused filter + GROUP BY insert (HBM-table strategy), or — radix-
+    # partitioned strategy (pp.hip, high cardinality) — the whole step's level passes + LDS
+    # aggregation, whose launches together touch the §8d bytes once
+    if partitioned:
+        pp_names = [k for k in prof if k.startswith("pp_") and k != "pp_probe"]
+        ins_ms = sum(prof[k][0] for k in pp_names)
+        ins_n = args.steps
+        kernel_name = "+".join(sorted(pp_names)) + " (one step)"
+    else:
+        ins_ms, ins_n = prof.get("agg_insert", (0.0, 0))
+        kernel_name = "agg_insert"
+        if "part_direct" in prof:  # C3: the sort in the insert, the table stage in the finalize (part.hip)
+            ins_ms += prof["part_direct"][0]
+            kernel_name = "agg_insert+part_direct"
+    avg_ms = ins_ms / max(1, ins_n)
+    # algorithmic bytes of one insert launch (SURVEY.md §8d)
+    alg_bytes = algorithmic_bytes(cfg, runner.inputs[0], rows, sel, n_groups, runner.result_types, kstr)
+    achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+    out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                       "kernel": kernel_name, "kernel_avg_ms": avg_ms, "kernel_launches": ins_n,
+                       "algorithmic_bytes_per_launch": alg_bytes}
+    out["kernels_ms_per_step"] = {k: v[0] / args.steps for k, v in prof.items()}
     # measured PMC traffic (rocprofv3 --pmc, committed under profiles/) if present for this config
     traffic, tsrc = load_traffic(cfg)
     if traffic:

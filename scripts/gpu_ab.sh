@@ -8,7 +8,7 @@ export DBGPU_LIB=$PWD/databend_amd/libdbgpu_agg_exp.so
 for rep in ${REPS:-1}; do
 for v in $VARIANTS; do
   echo "[$(date +%T)] $v"
-  env $(echo $v | tr ';' ' ') timeout -k 10 300 python -u bench.py --config $CFG --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline > $O/ab.json 2> $O/ab.err || { tail -20 $O/ab.err; exit 1; }
+  env $(echo $v | tr ';' ' ') timeout -k 10 300 python -u bench.py --full --config $CFG --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline > $O/ab.json 2> $O/ab.err || { tail -20 $O/ab.err; exit 1; }
   python3 -c "import json; d=json.loads(open('$O/ab.json').read().strip().splitlines()[-1]); print('  $v', round(d['ms_per_step'],4), 'ms frac', round(d['roofline']['frac'],4), {k: round(v,3) for k,v in d.get('kernels_ms_per_step',{}).items()})"
 done
 done

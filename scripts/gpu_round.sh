@@ -15,8 +15,9 @@ if [ -z "$SKIP_TESTS" ]; then
   cat gpurun_out/smoke.log
 fi
 step bench
-timeout -k 10 300 python -u bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || { echo "bench failed"; tail -30 gpurun_out/bench.err; exit 1; }
-cat gpurun_out/bench.json
+O=${OUT:-bench_out}; mkdir -p $O
+timeout -k 10 300 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -30 $O/bench.err; exit 1; }
+cat $O/bench.json
 for c in ${CONFIGS:-2 1 3 4 5}; do
   step "rocprof config $c"
   st=20; [ "$c" != 2 ] && st=${STEPS:-3}
