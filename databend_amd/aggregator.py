@@ -285,11 +285,19 @@ class AggregateHashTable:
         check(lib().dbg_agg_finalize(self.h, C.byref(n), sb))
         return n.value, list(sb)
 
+    def result_string_bytes(self) -> List[int]:
+        """After finalize(): payload bytes of each aggregate's result column (0 unless it is a
+        String, i.e. MIN/MAX of a String argument) — dbg_agg_result_string_bytes."""
+        n = len(self.params.aggregate_functions)
+        ab = (C.c_uint64 * max(1, n))()
+        check(lib().dbg_agg_result_string_bytes(self.h, ab))
+        return list(ab)[:n]
+
     def merge_result(self) -> DataBlock:
         """All groups as one host DataBlock [agg results..., group cols...]
         (TransformFinalAggregate output order, AGG/transform_aggregate_final.rs:128-133)."""
         n, sbytes = self.finalize()
-        aggs, keys = self._out_buffers(n, sbytes)
+        aggs, keys = self._out_buffers(n, sbytes, self.result_string_bytes())
         out_a = (abi.dbg_out_column * max(1, len(aggs)))()
         out_k = (abi.dbg_out_column * max(1, len(keys)))()
         for i, b in enumerate(aggs):
@@ -306,7 +314,8 @@ class AggregateHashTable:
         from .device import DeviceColumn, empty
         n, sbytes = self.finalize()
         gt = self.params.group_data_types
-        aggs = [empty(f.return_type(), n) for f in self.params.aggregate_functions]
+        abytes = self.result_string_bytes()
+        aggs = [empty(f.return_type(), n, string_bytes=abytes[i]) for i, f in enumerate(self.params.aggregate_functions)]
         keys = [empty(t, n, string_bytes=sbytes[i]) for i, t in enumerate(gt)]
         out_a = (abi.dbg_out_column * max(1, len(aggs)))()
         out_k = (abi.dbg_out_column * max(1, len(keys)))()
@@ -347,7 +356,7 @@ class AggregateHashTable:
         cols = [self._to_column(b, n) for b in states] + [self._to_column(b, n) for b in keys]
         return DataBlock(cols)
 
-    def _out_buffers(self, n, sbytes):
+    def _out_buffers(self, n, sbytes, abytes=None):
         def buf(t: DataType, strbytes=0):
             if t.type_id == abi.STRING:
                 data = np.zeros(max(1, strbytes), np.uint8)
@@ -359,7 +368,7 @@ class AggregateHashTable:
             return dict(t=t, data=data, offs=offs, val=val,
                         ptrs=(data.ctypes.data, offs.ctypes.data if offs is not None else None,
                               val.ctypes.data if val is not None else None))
-        aggs = [buf(f.return_type()) for f in self.params.aggregate_functions]
+        aggs = [buf(f.return_type(), abytes[i] if abytes else 0) for i, f in enumerate(self.params.aggregate_functions)]
         keys = [buf(t, sbytes[i]) for i, t in enumerate(self.params.group_data_types)]
         return aggs, keys
 

@@ -168,8 +168,8 @@ static int result_type_of(const dbg_agg_spec& s, dbg_datatype* out) {
             break;
         case DBG_AGG_MIN: case DBG_AGG_MAX:
             // Boolean: MinMaxAnyState<BooleanType> (false < true; the 0/1 value in an i64 state word,
-            // one byte per row in results and borsh Option<bool>); String stays on the CPU path
-            if (t == DBG_STRING) return fail(DBG_ERR_UNSUPPORTED, "min/max: String arguments stay on the CPU path");
+            // one byte per row in results and borsh Option<bool>); String: MinMaxAnyState<StringType>,
+            // a reference to the winning input row as the state (MMK_STR)
             r = dbg_datatype{t, s.arg.precision, s.arg.scale, 0, 0};
             break;
         default: return fail(DBG_ERR_INVALID, "unknown aggregate kind");
@@ -230,6 +230,7 @@ int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtyp
         A.sumk = t == DBG_DECIMAL128 ? SUMK_I128 : (is_float(t) ? SUMK_F64 : SUMK_I64);
         A.mmk = is_unsigned_i(t) ? MMK_U64 : (is_float(t) ? MMK_F64 : MMK_I64);
         if (t == DBG_DECIMAL128 && s.arg.precision > 18) A.mmk = MMK_I128;
+        if (t == DBG_STRING && (s.kind == DBG_AGG_MIN || s.kind == DBG_AGG_MAX)) A.mmk = MMK_STR;
         A.w0 = word;
         switch (A.kind) {
             case DBG_AGG_COUNT: A.nwords = 1; break;
@@ -249,6 +250,7 @@ int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtyp
         A.scale_add = (A.kind == DBG_AGG_AVG && t == DBG_DECIMAL128) ? (int)rt.scale - (int)s.arg.scale : 0;
         A.avg_round = sql_avg && t == DBG_DECIMAL128;
         A.res_width = (int)type_width(rt.type);
+        if (is_str_minmax(A)) A.res_width = 8;  // the result writers emit the row reference; dbg_agg_result gathers the bytes
         A.ser_flags = 0;
         if (s.kind != DBG_AGG_COUNT) {
             if (s.or_null) A.ser_flags |= SER_OR_NULL;
@@ -310,7 +312,8 @@ int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtyp
     if (!vbits) S.pp_avoff = S.pp_rw_raw;
     S.pp_rw_state = S.pp_kw + 8 * (u32)S.n_words;
     S.pp_sw = 1 + S.pp_kw / 8 + (u32)S.n_words;
-    S.pp_ok = S.pp_rw_raw <= 256 && S.pp_rw_state <= 256 && vbits <= 64 && S.pp_sw <= 64;
+    // String MIN/MAX states are row references local to this handle's HBM table: never partitioned
+    S.pp_ok = S.pp_rw_raw <= 256 && S.pp_rw_state <= 256 && vbits <= 64 && S.pp_sw <= 64 && !has_str_minmax(S);
     return DBG_OK;
 }
 
@@ -1593,6 +1596,35 @@ static int ensure_buf(u64** p, u64* cap, u64 n) {
     return dev_alloc((void**)p, *cap * 8);
 }
 
+// Payload bytes of every String MIN/MAX result column (h->agg_string_bytes): one pass over the
+// table's groups that follows each state's row reference to its length.
+static int str_agg_totals(dbg_agg_handle* h) {
+    const Spec& S = h->spec;
+    if (!has_str_minmax(S)) return DBG_OK;
+    h->agg_string_bytes.assign(S.n_aggs, 0);
+    if (h->n_groups == 0) return DBG_OK;
+    u64* dtot = nullptr;
+    RETURN_IF(dev_alloc((void**)&dtot, 8ull * S.n_aggs));
+    hipError_t e = hipMemsetAsync(dtot, 0, 8ull * S.n_aggs, h->stream);
+    if (e == hipSuccess) {
+        prof::Scope ps("str_agg_bytes", h->stream);
+        launch_str_agg_bytes(h->stream, h->dspec, h->dbatches, table_desc(h), dtot);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h->agg_string_bytes.data(), dtot, 8ull * S.n_aggs, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(dtot);
+    if (e != hipSuccess) return fail(DBG_ERR_DEVICE, std::string("string aggregate sizes: ") + hipGetErrorString(e));
+    return DBG_OK;
+}
+
+int dbg_agg_result_string_bytes(dbg_agg_handle* h, uint64_t* agg_string_bytes) {
+    if (!h || !agg_string_bytes) return fail(DBG_ERR_INVALID, "null argument");
+    if (!h->finalized) return fail(DBG_ERR_INVALID, "dbg_agg_finalize must precede dbg_agg_result_string_bytes");
+    for (int a = 0; a < h->spec.n_aggs; ++a)
+        agg_string_bytes[a] = (is_str_minmax(h->spec.aggs[a]) && (size_t)a < h->agg_string_bytes.size()) ? h->agg_string_bytes[a] : 0;
+    return DBG_OK;
+}
+
 int dbg_agg_finalize(dbg_agg_handle* h, uint64_t* n_groups, uint64_t* string_bytes) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
     HIPCHECK(hipSetDevice(h->device));
@@ -1643,6 +1675,7 @@ int dbg_agg_finalize(dbg_agg_handle* h, uint64_t* n_groups, uint64_t* string_byt
             RETURN_IF(grow_table(h, pow2_at_least((u64)(h->n_groups * 2.0) + 1)));
             continue;  // positions depend on the slot layout: count again
         }
+        RETURN_IF(str_agg_totals(h));
         h->finalized = true;
         if (n_groups) *n_groups = h->n_groups;
         if (string_bytes)
@@ -1674,6 +1707,7 @@ int dbg_agg_result(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_column* 
 
 int dbg_agg_serialized_stride(dbg_agg_handle* h, uint32_t* stride) {
     if (!h || !stride) return fail(DBG_ERR_INVALID, "null argument");
+    REFUSE_STR_MINMAX(h, "dbg_agg_serialized_stride");
     for (int a = 0; a < h->spec.n_aggs; ++a) {
         if (h->src_kinds[a] == DBG_AGG_AVG_SQL)
             return fail(DBG_ERR_UNSUPPORTED, "serialized states: SQL avg is sum and count in the reference plan");
@@ -1684,6 +1718,7 @@ int dbg_agg_serialized_stride(dbg_agg_handle* h, uint32_t* stride) {
 
 int dbg_agg_result_serialized(dbg_agg_handle* h, dbg_out_column* out_states, dbg_out_column* out_keys, int on_device) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
+    REFUSE_STR_MINMAX(h, "dbg_agg_result_serialized");
     for (int a = 0; a < h->spec.n_aggs; ++a)
         if (h->src_kinds[a] == DBG_AGG_AVG_SQL)
             return fail(DBG_ERR_UNSUPPORTED, "serialized states: SQL avg is sum and count in the reference plan");
@@ -1706,8 +1741,8 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
                 if (on_device) HIPCHECK(hipMemcpy(out_keys[c].offsets, &z, 8, hipMemcpyHostToDevice));
                 else out_keys[c].offsets[0] = 0;
             }
-        for (int a = 0; a < S.n_aggs && ser; ++a)
-            if (out_aggs[a].offsets) {
+        for (int a = 0; a < S.n_aggs; ++a)
+            if ((ser || is_str_minmax(S.aggs[a])) && out_aggs[a].offsets) {
                 u64 z = 0;
                 if (on_device) HIPCHECK(hipMemcpy(out_aggs[a].offsets, &z, 8, hipMemcpyHostToDevice));
                 else out_aggs[a].offsets[0] = 0;
@@ -1749,7 +1784,8 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
             if (rc == DBG_OK) rc = tmp(n, (void**)&od.agg_valid[a]);
             continue;
         }
-        if (on_device) od.agg_data[a] = out_aggs[a].data;
+        if (is_str_minmax(S.aggs[a])) rc = tmp(n * 8, &od.agg_data[a]);  // row references, gathered below
+        else if (on_device) od.agg_data[a] = out_aggs[a].data;
         else rc = tmp(n * type_width(t.type), &od.agg_data[a]);
         if (rc == DBG_OK && t.nullable) {
             if (agg_always_valid(S.aggs[a])) od.all_valid |= 1u << a;
@@ -1819,6 +1855,32 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
                 if (out_aggs[a].data && ser_tot[a])
                     hipMemcpyAsync(out_aggs[a].data, od.agg_data[a], ser_tot[a], hipMemcpyDeviceToHost, h->stream);
     }
+    // String MIN/MAX: the row references the writers emitted -> offsets and bytes of the values
+    for (int a = 0; a < S.n_aggs && !ser; ++a) {
+        if (!is_str_minmax(S.aggs[a])) continue;
+        const u64 total = (size_t)a < h->agg_string_bytes.size() ? h->agg_string_bytes[a] : 0;
+        u64* offs = nullptr;
+        u8* data = nullptr;
+        if (on_device) {
+            offs = out_aggs[a].offsets;
+            data = (u8*)out_aggs[a].data;
+            if (!offs || (total && !data)) {
+                free_temps();
+                return fail(DBG_ERR_INVALID, "dbg_agg_result: a String aggregate needs offsets and data buffers");
+            }
+        } else if (tmp((n + 1) * 8, (void**)&offs) != DBG_OK || tmp(total, (void**)&data) != DBG_OK) {
+            free_temps();
+            return DBG_ERR_OOM;
+        }
+        {
+            prof::Scope ps("str_gather", h->stream);
+            launch_str_gather(h->stream, h->dbatches, a, (const u64*)od.agg_data[a], n, offs, data, total);
+        }
+        if (!on_device) {
+            if (out_aggs[a].offsets) hipMemcpyAsync(out_aggs[a].offsets, offs, (n + 1) * 8, hipMemcpyDeviceToHost, h->stream);
+            if (out_aggs[a].data && total) hipMemcpyAsync(out_aggs[a].data, data, total, hipMemcpyDeviceToHost, h->stream);
+        }
+    }
     for (int a = 0; a < S.n_aggs && !ser; ++a) {
         const dbg_datatype& t = h->result_types[a];
         if (t.nullable) {
@@ -1843,7 +1905,7 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
                 hipMemcpyAsync(out_keys[c].offsets, od.key_offsets[c], (n + 1) * 8, hipMemcpyDeviceToHost, h->stream);
         }
         for (int a = 0; a < S.n_aggs && !ser; ++a)
-            if (out_aggs[a].data)
+            if (out_aggs[a].data && !is_str_minmax(S.aggs[a]))
                 hipMemcpyAsync(out_aggs[a].data, od.agg_data[a], n * type_width(h->result_types[a].type), hipMemcpyDeviceToHost, h->stream);
     }
     HIPCHECK(hipMemcpyAsync(h->hcounters, h->counters, CNT_WORDS * 8, hipMemcpyDeviceToHost, h->stream));
@@ -1861,6 +1923,7 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
 int dbg_agg_set_strategy(dbg_agg_handle* h, int strategy) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
     if (strategy < DBG_STRATEGY_AUTO || strategy > DBG_STRATEGY_PARTITIONED) return fail(DBG_ERR_INVALID, "unknown strategy");
+    if (strategy == DBG_STRATEGY_PARTITIONED) REFUSE_STR_MINMAX(h, "dbg_agg_set_strategy(PARTITIONED)");
     if (h->table_rows || h->ppk[0].l1_n || h->ppk[1].l1_n)
         return fail(DBG_ERR_INVALID, "dbg_agg_set_strategy: the handle holds groups (call it after create or reset)");
     // AUTO switches only for records of <= 256 bytes (build_spec: pp_ok); a forced partitioned
@@ -2238,6 +2301,7 @@ int dbg_agg_finalize_into(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_c
 int dbg_agg_finalize_into_async(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_column* out_keys, uint64_t max_groups,
                                 const uint64_t* max_string_bytes) {
     if (!h || !out_aggs || !out_keys) return fail(DBG_ERR_INVALID, "null argument");
+    REFUSE_STR_MINMAX(h, "dbg_agg_finalize_into_async");
     if (h->fin.active) return fail(DBG_ERR_INVALID, "a finalize is already in flight: dbg_agg_finalize_wait first");
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(fin_setup(h, out_aggs, out_keys, max_groups, max_string_bytes));
@@ -2270,6 +2334,7 @@ int dbg_agg_record_layout(const dbg_agg_params* params, dbg_record_layout* out) 
     Spec S;
     std::vector<dbg_datatype> rt;
     RETURN_IF(build_spec(params, S, rt));
+    if (has_str_minmax(S)) return fail(DBG_ERR_UNSUPPORTED, "dbg_agg_record_layout: String min/max states are row references local to a handle");
     memset(out, 0, sizeof(*out));
     out->width = S.rec_width;
     out->state_off = S.rec_state_off;
@@ -2322,6 +2387,7 @@ static int legacy_layout(const Spec& S, u32 bits, LegacyLayout* L) {
 
 int dbg_agg_partition(dbg_agg_handle* h, uint32_t n_parts, int scheme, uint64_t* rec_counts, uint64_t* string_bytes) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
+    REFUSE_STR_MINMAX(h, "dbg_agg_partition");
     if (n_parts < 1 || n_parts > 256) return fail(DBG_ERR_UNSUPPORTED, "1..256 partitions");
     if (scheme < 0 || scheme > 2) return fail(DBG_ERR_INVALID, "scheme 0 (hash % n), 1 (radix bits) or 2 (legacy buckets)");
     if (scheme >= 1 && (n_parts & (n_parts - 1))) return fail(DBG_ERR_INVALID, "radix partitions must be a power of two");
@@ -2393,6 +2459,7 @@ int dbg_agg_partition(dbg_agg_handle* h, uint32_t n_parts, int scheme, uint64_t*
 
 int dbg_agg_export_records(dbg_agg_handle* h, void* dev_records, void* dev_strings) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
+    REFUSE_STR_MINMAX(h, "dbg_agg_export_records");
     if (!h->part_n) return fail(DBG_ERR_INVALID, "dbg_agg_partition must precede dbg_agg_export_records");
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(flush_pending(h));
@@ -2417,6 +2484,7 @@ int dbg_agg_capacity(dbg_agg_handle* h, uint64_t* slots) {
 // ---- fixed-capacity exchange (replicas + gather, low cardinality) ----
 int dbg_agg_export_fixed(dbg_agg_handle* h, void* dev_buf, uint64_t cap_records) {
     if (!h || !dev_buf) return fail(DBG_ERR_INVALID, "null argument");
+    REFUSE_STR_MINMAX(h, "dbg_agg_export_fixed");
     const Spec& S = h->spec;
     if (!S.inline_keys) return fail(DBG_ERR_UNSUPPORTED, "fixed export needs fixed-width (inline) group keys");
     if (h->cap + 1 > FIN_SMALL_SLOTS || h->pp) return fail(DBG_ERR_UNSUPPORTED, "fixed export is for small tables");
@@ -2437,6 +2505,7 @@ int dbg_agg_export_fixed(dbg_agg_handle* h, void* dev_buf, uint64_t cap_records)
 
 int dbg_agg_merge_fixed(dbg_agg_handle* h, const void* dev_bufs, int32_t n_bufs, uint64_t cap_records) {
     if (!h || !dev_bufs || n_bufs < 1) return fail(DBG_ERR_INVALID, "bad argument");
+    REFUSE_STR_MINMAX(h, "dbg_agg_merge_fixed");
     const Spec& S = h->spec;
     if (!S.inline_keys) return fail(DBG_ERR_UNSUPPORTED, "fixed merge needs fixed-width (inline) group keys");
     if (h->pp) return fail(DBG_ERR_UNSUPPORTED, "fixed merge: the handle runs partitioned (high cardinality)");
@@ -2520,6 +2589,7 @@ static int merge_record_batch(dbg_agg_handle* h, const u8* base, u64 n, const u8
 int dbg_agg_merge_records(dbg_agg_handle* h, const void* dev_records, const void* dev_strings, int32_t n_segments,
                           const uint64_t* seg_records, const uint64_t* seg_string_bytes) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
+    REFUSE_STR_MINMAX(h, "dbg_agg_merge_records");
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(flush_pending(h));
     h->finalized = false;
@@ -2552,7 +2622,8 @@ int dbg_agg_compact(dbg_agg_handle* h, int* compacted) {
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(flush_pending(h));
     const Spec& S = h->spec;
-    if (h->pp || S.inline_keys) return DBG_OK;
+    // String MIN/MAX states point into the retained input: nothing can be released (a no-op)
+    if (h->pp || S.inline_keys || has_str_minmax(S)) return DBG_OK;
     u64 n = 0, sb = 0;
     RETURN_IF(dbg_agg_partition(h, 1, 0, &n, &sb));
     DevBuf rb, strb;
@@ -2600,6 +2671,7 @@ int dbg_agg_retained_bytes(dbg_agg_handle* h, uint64_t* bytes) {
 int dbg_agg_merge_serialized(dbg_agg_handle* h, const dbg_column* state_cols, const dbg_column* group_cols, uint64_t rows,
                              int on_device) {
     if (!h || (!state_cols && h->spec.n_aggs) || !group_cols) return fail(DBG_ERR_INVALID, "null argument");
+    REFUSE_STR_MINMAX(h, "dbg_agg_merge_serialized");
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(flush_pending(h));
     h->finalized = false;

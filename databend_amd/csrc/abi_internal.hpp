@@ -126,7 +126,8 @@ struct dbg_agg_handle {
     bool finalized = false;
     u64 n_groups = 0;
     std::vector<u64> string_bytes;
-    u64* d_pos = nullptr;      // scanned per-block group counts
+    std::vector<u64> agg_string_bytes;  // payload bytes of each String MIN/MAX result column (dbg_agg_finalize)
+    u64* d_pos = nullptr;     // scanned per-block group counts
     u64* d_str_pos = nullptr;  // [n_keys][blocks] scanned per column
     u64 pos_cap = 0, str_pos_cap = 0;
     // partition state
@@ -245,6 +246,21 @@ struct dbg_agg_handle {
     // host-block staging (dbg_agg_set_host_staging, host_stage.hpp)
     hstage::Stage stage;
 };
+
+// String MIN/MAX (MMK_STR): the state is a reference into this handle's retained input, so every
+// entry point that ships, re-encodes or compacts states refuses such a handle (REFUSE_STR_MINMAX)
+inline bool is_str_minmax(const DAgg& A) { return (A.kind == DBG_AGG_MIN || A.kind == DBG_AGG_MAX) && A.mmk == MMK_STR; }
+inline bool has_str_minmax(const Spec& S) {
+    for (int a = 0; a < S.n_aggs; ++a)
+        if (is_str_minmax(S.aggs[a])) return true;
+    return false;
+}
+#define REFUSE_STR_MINMAX(h, what)                                                                              \
+    do {                                                                                                        \
+        if (has_str_minmax((h)->spec))                                                                          \
+            return fail(DBG_ERR_UNSUPPORTED, std::string(what) + ": String min/max states are row references " \
+                                                                 "local to the handle (dbg_agg_result only)"); \
+    } while (0)
 
 // handle helpers abi.hip defines for the other units
 int dev_alloc(void** p, size_t bytes);

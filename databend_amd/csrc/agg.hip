@@ -200,7 +200,7 @@ __device__ __forceinline__ u64 lds_entry_hash(const Spec& S, const BatchDesc& B,
     return group_hash(B.keys, S.n_keys, ref_row(e));
 }
 
-template <bool INLINE, bool RECORDS>
+template <bool INLINE, bool RECORDS, bool STR = true>  // STR: see apply_row
 __device__ __forceinline__ void flush_lds_direct(const Spec& S, const BatchDesc* batches, const BatchDesc& B, u64* lds,
                                                  u32 lds_slots, u32 sw, u32 nt, const TableDesc& t, u32& my_claims) {
     for (u32 s = threadIdx.x; s < lds_slots; s += nt) {
@@ -215,7 +215,7 @@ __device__ __forceinline__ void flush_lds_direct(const Spec& S, const BatchDesc*
             continue;
         }
         my_claims += claimed ? 1 : 0;
-        apply_state<AS_GLB, false, AS_LDS>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), p);
+        apply_state<AS_GLB, false, AS_LDS, STR>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), p, batches);
     }
 }
 
@@ -232,7 +232,7 @@ __device__ __forceinline__ void lds_table_init(const Spec& S, u64* lds, u32 lds_
 
 // lcount: [0] LDS claims, [1] HBM claims, [2] parked entries, [3] last-workgroup flag.
 // Ends with the workgroup's HBM claims added to the table counter.
-template <bool INLINE, bool RECORDS>
+template <bool INLINE, bool RECORDS, bool STR = true>
 __device__ __forceinline__ void block_flush(const Spec& S, const BatchDesc* batches, const BatchDesc& B, u64* lds, u32 lds_slots, u32 sw,
                             u32* lcount, u32 nt, const TableDesc& t, u32 my_claims) {
     const u32 lmask = lds_slots - 1;
@@ -255,7 +255,7 @@ __device__ __forceinline__ void block_flush(const Spec& S, const BatchDesc* batc
             if (threadIdx.x == 0) st_sc1(counts + blockIdx.x, lcount[2]);
         } else {
             if (threadIdx.x == 0) st_sc1(counts + blockIdx.x, 0);
-            flush_lds_direct<INLINE, RECORDS>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
+            flush_lds_direct<INLINE, RECORDS, STR>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
         }
         // Hand-off without release fences (MI355X_MICROARCH.md, inter-workgroup visibility, valid
         // forms): parked words are stored sc1 (write-through past the XCD's L2); every storing
@@ -293,7 +293,7 @@ __device__ __forceinline__ void block_flush(const Spec& S, const BatchDesc* batc
                 u64 h = lds_entry_hash<INLINE, RECORDS>(S, B, e);
                 int ls = lds_find<INLINE>(S, batches, B.keys, INLINE ? 0 : ref_row(e), e, h, lds, lmask, sw, lcount, llimit);
                 if (ls >= 0) {
-                    apply_state<AS_LDS, true>(S, asp<AS_LDS>(lds + (u64)ls * sw), r);
+                    apply_state<AS_LDS, true, AS_GLB, STR>(S, asp<AS_LDS>(lds + (u64)ls * sw), r, batches);
                     continue;
                 }
                 bool claimed;
@@ -303,13 +303,13 @@ __device__ __forceinline__ void block_flush(const Spec& S, const BatchDesc* batc
                     continue;
                 }
                 my_claims += claimed ? 1 : 0;
-                apply_state<AS_GLB, true>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), r);
+                apply_state<AS_GLB, true, AS_GLB, STR>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), r, batches);
             }
             __syncthreads();
-            flush_lds_direct<INLINE, RECORDS>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
+            flush_lds_direct<INLINE, RECORDS, STR>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
         }
     } else {
-        flush_lds_direct<INLINE, RECORDS>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
+        flush_lds_direct<INLINE, RECORDS, STR>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
     }
     if (my_claims) atomicAdd(&lcount[1], my_claims);
     __syncthreads();
@@ -369,8 +369,8 @@ __device__ __forceinline__ void insert_one(const Spec& S, const BatchDesc* batch
     const u64* rec = RECORDS ? (const u64*)(B.rec_base + i * (u64)B.rec_width + S.rec_state_off) - 1 : nullptr;
     if (ls >= 0) {
         wptr<AS_LDS> st = asp<AS_LDS>(lds + (u64)ls * sw);
-        if (RECORDS) apply_state<AS_LDS>(S, st, rec);
-        else apply_row<AS_LDS>(S, st, B, i);
+        if (RECORDS) apply_state<AS_LDS>(S, st, rec, batches);
+        else apply_row<AS_LDS>(S, st, B, i, batches, bid);
         return;
     }
     bool claimed;
@@ -381,8 +381,8 @@ __device__ __forceinline__ void insert_one(const Spec& S, const BatchDesc* batch
     }
     my_claims += claimed ? 1 : 0;
     wptr<AS_GLB> st = asp<AS_GLB>(t.slots + gs * t.stride_words);
-    if (RECORDS) apply_state<AS_GLB>(S, st, rec);
-    else apply_row<AS_GLB>(S, st, B, i);
+    if (RECORDS) apply_state<AS_GLB>(S, st, rec, batches);
+    else apply_row<AS_GLB>(S, st, B, i, batches, bid);
 }
 
 // Every FLUSH_ROUND rounds: a full LDS table is flushed to HBM and started over (the
@@ -754,7 +754,7 @@ __device__ __forceinline__ void flush_kc(const Spec& S, const BatchDesc* batches
             continue;
         }
         my_claims += claimed ? 1 : 0;
-        apply_state<AS_GLB, false, AS_LDS>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), p);
+        apply_state<AS_GLB, false, AS_LDS>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), p, batches);
     }
 }
 
@@ -821,7 +821,7 @@ __global__ void __launch_bounds__(STR1_NT) agg_insert_str1_kernel(const Spec* __
             atomicAdd(&lcount[5], (u32)__popcll(mm));
         }
         if (ls >= 0) {
-            apply_row<AS_LDS>(S, asp<AS_LDS>(lds + (u64)ls * lsw), B, i);
+            apply_row<AS_LDS>(S, asp<AS_LDS>(lds + (u64)ls * lsw), B, i, batches, bid);
             return;
         }
         if (kExperiments && (xmode & 4)) return;
@@ -832,7 +832,7 @@ __global__ void __launch_bounds__(STR1_NT) agg_insert_str1_kernel(const Spec* __
             return;
         }
         my_claims += claimed ? 1 : 0;
-        apply_row<AS_GLB>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), B, i);
+        apply_row<AS_GLB>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), B, i, batches, bid);
     };
 
     // A full LDS table is flushed to HBM and started over only while it serves few rows (hit rate
@@ -1093,7 +1093,7 @@ __device__ __forceinline__ void short_tree_flush(const Spec& S, const BatchDesc*
                 pos = (pos + 1) & lmask;
             }
             if (ls >= 0) {
-                apply_state<AS_LDS, true>(S, asp<AS_LDS>(lds + (u64)ls * sw), r);
+                apply_state<AS_LDS, true>(S, asp<AS_LDS>(lds + (u64)ls * sw), r, batches);
                 continue;
             }
             // the merge table is full: this row goes to HBM by itself
@@ -1105,7 +1105,7 @@ __device__ __forceinline__ void short_tree_flush(const Spec& S, const BatchDesc*
                 continue;
             }
             my_claims += claimed ? 1 : 0;
-            apply_state<AS_GLB, true>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), r);
+            apply_state<AS_GLB, true>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), r, batches);
         }
         __syncthreads();
         toff += (n_nodes + SHORT_FANIN - 1) / SHORT_FANIN;
@@ -1197,7 +1197,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6)))
             s = (s + 1) & lmask;
         }
         if (ls >= 0) {
-            apply_row<AS_LDS>(S, asp<AS_LDS>(lds + (u64)ls * sw), B, i);
+            apply_row<AS_LDS>(S, asp<AS_LDS>(lds + (u64)ls * sw), B, i, batches, bid);
             return;
         }
         bool claimed;
@@ -1207,7 +1207,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6)))
             return;
         }
         my_claims += claimed ? 1 : 0;
-        apply_row<AS_GLB>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), B, i);
+        apply_row<AS_GLB>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), B, i, batches, bid);
     };
     auto process = [&](u64 i, const ShortRow& r) __attribute__((always_inline)) {
         const u64 l0 = r.o[1] - r.o[0], l1 = r.o[3] - r.o[2];
@@ -1392,8 +1392,8 @@ __global__ void __launch_bounds__(BLOCK) agg_retry_kernel(const Spec* __restrict
                 continue;
             }
             wptr<AS_GLB> st = asp<AS_GLB>(t.slots + gs * t.stride_words);
-            if (B.is_records) apply_state<AS_GLB>(S, st, (const u64*)(B.rec_base + i * (u64)B.rec_width + S.rec_state_off) - 1);
-            else apply_row<AS_GLB>(S, st, B, i);
+            if (B.is_records) apply_state<AS_GLB>(S, st, (const u64*)(B.rec_base + i * (u64)B.rec_width + S.rec_state_off) - 1, batches);
+            else apply_row<AS_GLB>(S, st, B, i, batches, bid);
         } else {
             const u64* r = recs_list + (k - n_rows) * t.stride_words;
             u64 key = r[0];
@@ -1408,7 +1408,7 @@ __global__ void __launch_bounds__(BLOCK) agg_retry_kernel(const Spec* __restrict
                 atomicOr((unsigned long long*)(t.counters + CNT_ERR), (unsigned long long)ERR_OVF_LOST);
                 continue;
             }
-            apply_state<AS_GLB>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), r);
+            apply_state<AS_GLB>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), r, batches);
         }
         if (claimed) atomicAdd((unsigned long long*)(t.counters + CNT_CLAIMS), 1ULL);
     }
@@ -2031,11 +2031,11 @@ __device__ __forceinline__ void fused_finalize(const Spec& S, const BatchDesc* b
 
 // merge_states of a parked partial state (sc1 loads) into a slot; COUNT(*) alone (CO): one add
 template <int AS, bool CO>
-__device__ __forceinline__ void merge_parked(const Spec& S, u64* st, const u64* r, u64 c1) {
+__device__ __forceinline__ void merge_parked(const Spec& S, const BatchDesc* batches, u64* st, const u64* r, u64 c1) {
     if constexpr (CO) {  // c1: the parked count, loaded with the entry
         if (c1) at_add<AS>(asp<AS>(st + 1), c1);
     } else {
-        apply_state<AS, true>(S, asp<AS>(st), r);
+        apply_state<AS, true, AS_GLB, false>(S, asp<AS>(st), r, batches);  // fast kernel: no String MIN/MAX (fast_eligible)
     }
 }
 
@@ -2300,7 +2300,7 @@ __device__ __forceinline__ void fused_chain(const Spec& S, const BatchDesc* batc
     // records); returns the parked entries (uniform)
     auto park = [&](u64* dst) -> u64 {
         if (lcount[0] > SCR_ENTRIES) {
-            flush_lds_direct<true, false>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
+            flush_lds_direct<true, false, false>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
             my_ovf += threadIdx.x == 0 ? 1u : 0u;
             return 0;
         }
@@ -2371,7 +2371,7 @@ __device__ __forceinline__ void fused_chain(const Spec& S, const BatchDesc* batc
         if (k >= cnt) continue;
         const int ls = lds_find<true>(S, batches, B.keys, 0, e, 0, lds, lmask, sw, lcount, llimit);
         if (ls >= 0) {
-            merge_parked<AS_LDS, CO>(S, lds + (u64)ls * sw, r, c1);
+            merge_parked<AS_LDS, CO>(S, batches, lds + (u64)ls * sw, r, c1);
             continue;
         }
         bool claimed;
@@ -2382,7 +2382,7 @@ __device__ __forceinline__ void fused_chain(const Spec& S, const BatchDesc* batc
             continue;
         }
         my_claims += claimed ? 1 : 0;
-        merge_parked<AS_GLB, CO>(S, t.slots + gs * t.stride_words, r, c1);
+        merge_parked<AS_GLB, CO>(S, batches, t.slots + gs * t.stride_words, r, c1);
     }
     __syncthreads();
     const u64 gp = park(grows + (u64)g * SCR_ENTRIES * sw);
@@ -2426,7 +2426,7 @@ __device__ __forceinline__ void fused_chain(const Spec& S, const BatchDesc* batc
         if (k >= cnt) continue;
         u64 slot;
         if (view_find(lds, t, e, vclaims, slot)) {
-            merge_parked<AS_LDS, CO>(S, lds + slot * sw, r, c1);
+            merge_parked<AS_LDS, CO>(S, batches, lds + slot * sw, r, c1);
         } else {
             push_ovf_rec<true>(S, t, e, r);
             bad = 1;
@@ -2499,7 +2499,7 @@ __device__ __forceinline__ void fused_chain_tagged(const Spec& S, const BatchDes
     // possible overflow pushes ride on the ticket (uniform: lcount[0] is final).
     auto flush_if_large = [&]() -> bool {
         if (lcount[0] <= SCR_ENTRIES) return false;
-        flush_lds_direct<true, false>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
+        flush_lds_direct<true, false, false>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
         my_ovf += threadIdx.x == 0 ? 1u : 0u;
         return true;
     };
@@ -2792,7 +2792,7 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
         if (ls >= 0) {
             wptr<AS_LDS> st = asp<AS_LDS>(lds + (u64)ls * sw);
             if (CO) at_add<AS_LDS>(st + 1, 1ULL);
-            else apply_row<AS_LDS>(S, st, B, i);
+            else apply_row<AS_LDS, false>(S, st, B, i, batches, bid);
             return;
         }
         bool claimed;
@@ -2805,7 +2805,7 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
         my_claims += claimed ? 1 : 0;
         wptr<AS_GLB> gst = asp<AS_GLB>(t.slots + gs * t.stride_words);
         if (CO) at_add<AS_GLB>(gst + 1, 1ULL);
-        else apply_row<AS_GLB>(S, gst, B, i);
+        else apply_row<AS_GLB, false>(S, gst, B, i, batches, bid);
     };
 
     u32 qn = 0;  // wave-uniform queue length
@@ -3114,7 +3114,7 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
         fused_chain<T, CO>(S, batches, B, lds, lds_slots, sw, lcount, NT, t, my_claims, my_ovf, ff);
         return;
     }
-    block_flush<true, false>(S, batches, B, lds, lds_slots, sw, lcount, NT, t, my_claims);
+    block_flush<true, false, false>(S, batches, B, lds, lds_slots, sw, lcount, NT, t, my_claims);
     if (kPhaseTrace && ff.trace && threadIdx.x == 0) atomicMax((unsigned long long*)ff.trace + 3, (unsigned long long)__builtin_amdgcn_s_memrealtime());
     if (ff.on) fused_finalize(S, batches, t, lds, ff);
 }
@@ -3186,6 +3186,10 @@ static void launch_fast_t(hipStream_t s, const Spec* dspec, const BatchDesc* bat
 // Host-side eligibility for the fast path (hb = host copy of the batch descriptor).
 static bool fast_eligible(const Spec& S, const BatchDesc& hb, bool records) {
     if (records || !S.inline_keys || S.n_keys != 1 || S.key_types[0].nullable) return false;
+    // String MIN/MAX: the kernel is compiled without that update (apply_row<AS, false>); the
+    // generic insert stages and flushes such states
+    for (int a = 0; a < S.n_aggs; ++a)
+        if ((S.aggs[a].kind == DBG_AGG_MIN || S.aggs[a].kind == DBG_AGG_MAX) && S.aggs[a].mmk == MMK_STR) return false;
     const DCol& k = hb.keys[0];
     int ty = k.type;
     bool intlike = (ty >= DBG_INT8 && ty <= DBG_UINT64) || ty == DBG_DATE || ty == DBG_TIMESTAMP;
@@ -3610,4 +3614,81 @@ void launch_ser_compact(hipStream_t s, const u8* lens, const u8* src, u32 stride
     hipLaunchKernelGGL(ser_lengths_kernel, dim3((u32)blocks), dim3(256), 0, s, lens, n, offs);
     launch_exclusive_scan(s, offs, n + 1, total);
     if (n) hipLaunchKernelGGL(ser_copy_kernel, dim3((u32)blocks), dim3(256), 0, s, src, stride, n, offs, dst);
+}
+
+// ------------------------------------------------------------------------------------------
+// String MIN/MAX results (MMK_STR): the state word of a group is a reference to the winning input
+// row; the result column's offsets and bytes are gathered from the retained input.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ StrRef str_ref_value(const BatchDesc* batches, int a, u64 ref) {
+    return dcol_str(batches[ref_bid(ref)].args[a], ref_row(ref));
+}
+
+// totals[a] (zeroed) += payload bytes of String aggregate a over the groups of the table; groups
+// without a value (STR_REF_NONE: every argument NULL) count nothing
+__global__ void __launch_bounds__(BLOCK) str_agg_bytes_kernel(const Spec* __restrict__ spec, const BatchDesc* __restrict__ batches,
+                                                             TableDesc t, u64* totals) {
+    const Spec& S = *spec;
+    for (int a = 0; a < S.n_aggs; ++a) {
+        const DAgg& A = S.aggs[a];
+        if ((A.kind != DBG_AGG_MIN && A.kind != DBG_AGG_MAX) || A.mmk != MMK_STR) continue;  // uniform
+        u64 acc = 0;
+        for (u64 s = blockIdx.x * (u64)BLOCK + threadIdx.x; s <= t.cap; s += (u64)gridDim.x * BLOCK) {
+            const u64* st = t.slots + s * t.stride_words;
+            if (st[0] == SLOT_EMPTY) continue;
+            const u64 ref = st[A.w0];
+            if (ref != STR_REF_NONE) acc += str_ref_value(batches, a, ref).len;
+        }
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        if ((threadIdx.x & 63) == 0 && acc) atomicAdd((unsigned long long*)(totals + a), (unsigned long long)acc);
+    }
+}
+
+void launch_str_agg_bytes(hipStream_t s, const Spec* dspec, const BatchDesc* batches, const TableDesc& t, u64* totals) {
+    u64 blocks = (t.cap + 1 + BLOCK - 1) / BLOCK;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(str_agg_bytes_kernel, dim3((u32)blocks), dim3(BLOCK), 0, s, dspec, batches, t, totals);
+}
+
+// offs[i] = length of group i's value (0 for STR_REF_NONE), offs[n] = 0: scanned into offsets next
+__global__ void __launch_bounds__(BLOCK) str_gather_lengths_kernel(const BatchDesc* __restrict__ batches, int a,
+                                                                  const u64* __restrict__ refs, u64 n, u64* __restrict__ offs) {
+    for (u64 i = blockIdx.x * (u64)BLOCK + threadIdx.x; i <= n; i += (u64)gridDim.x * BLOCK) {
+        u64 len = 0;
+        if (i < n) {
+            const u64 ref = refs[i];
+            if (ref != STR_REF_NONE) len = str_ref_value(batches, a, ref).len;
+        }
+        offs[i] = len;
+    }
+}
+
+// The bytes: STR_GATHER_LANES consecutive lanes copy one string, a byte per lane and step
+// (consecutive lanes, consecutive bytes on both sides; the strings start at any address).  A value
+// that would pass cap_bytes (the total dbg_agg_finalize reported) is not written.
+#define STR_GATHER_LANES 16
+__global__ void __launch_bounds__(BLOCK) str_gather_bytes_kernel(const BatchDesc* __restrict__ batches, int a,
+                                                                const u64* __restrict__ refs, u64 n, const u64* __restrict__ offs,
+                                                                u8* __restrict__ data, u64 cap_bytes) {
+    const u32 sub = threadIdx.x % STR_GATHER_LANES;
+    const u64 per = (u64)gridDim.x * (BLOCK / STR_GATHER_LANES);
+    for (u64 i = blockIdx.x * (u64)(BLOCK / STR_GATHER_LANES) + threadIdx.x / STR_GATHER_LANES; i < n; i += per) {
+        const u64 ref = refs[i];
+        if (ref == STR_REF_NONE) continue;
+        const StrRef r = str_ref_value(batches, a, ref);
+        const u64 o = offs[i];
+        if (o + r.len > cap_bytes) continue;
+        for (u64 k = sub; k < r.len; k += STR_GATHER_LANES) data[o + k] = gld<u8>(r.p + k);
+    }
+}
+
+void launch_str_gather(hipStream_t s, const BatchDesc* batches, int a, const u64* refs, u64 n, u64* offs, u8* data, u64 cap_bytes) {
+    u64 blocks = (n + BLOCK) / BLOCK;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(str_gather_lengths_kernel, dim3((u32)blocks), dim3(BLOCK), 0, s, batches, a, refs, n, offs);
+    launch_exclusive_scan(s, offs, n + 1, nullptr);
+    if (!n || !cap_bytes) return;
+    u64 gblocks = (n + BLOCK / STR_GATHER_LANES - 1) / (BLOCK / STR_GATHER_LANES);
+    if (gblocks > 16384) gblocks = 16384;
+    hipLaunchKernelGGL(str_gather_bytes_kernel, dim3((u32)gblocks), dim3(BLOCK), 0, s, batches, a, refs, n, offs, data, cap_bytes);
 }

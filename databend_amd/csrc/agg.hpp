@@ -325,6 +325,12 @@ bool insert_can_fuse(const Spec& S, const BatchDesc& hb, u64 cap);
 void launch_write_results(hipStream_t s, const Spec* dspec, const Spec& hspec, const BatchDesc* batches, const TableDesc& t,
                           const u64* pos /* scanned hist */, const u64* str_pos, const OutDesc& out);
 void launch_pack_bits(hipStream_t s, const u8* bytes, u64 n, u8* bits);
+// String MIN/MAX (MMK_STR) results.  totals[a] (n_aggs words, zeroed) += payload bytes of String
+// aggregate a over the table's groups.
+void launch_str_agg_bytes(hipStream_t s, const Spec* dspec, const BatchDesc* batches, const TableDesc& t, u64* totals);
+// refs: one state word per group as the result writers emit it (STR_REF_NONE = NULL) -> offs
+// (n + 1 offsets) and the bytes of aggregate a's values in data (cap_bytes: what data holds)
+void launch_str_gather(hipStream_t s, const BatchDesc* batches, int a, const u64* refs, u64 n, u64* offs, u8* data, u64 cap_bytes);
 void launch_export_fixed(hipStream_t s, const Spec* dspec, const BatchDesc* batches, const TableDesc& t, u8* buf, u64 cap_records,
                          int recycle);
 void launch_export(hipStream_t s, const Spec* dspec, const Spec& hspec, const BatchDesc* batches, const TableDesc& t,

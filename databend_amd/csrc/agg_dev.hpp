@@ -42,9 +42,44 @@ __device__ __forceinline__ void set_flag(wptr<AS> st, int fw, int bit) {
     if (!(st[fw] & m)) at_or<AS>(st + fw, m);
 }
 
-// accumulate_keys of every aggregate for input row i into the slot at st (word 0 = entry).
+// String MIN/MAX (MinMaxAnyState<StringType, CMP>, aggregate_min_max_any.rs:131-145; change_if of
+// CmpMin / CmpMax, aggregate_scalar_state.rs:65-95).  The state word is a reference to the winning
+// input row, (bid << 32) | row, STR_REF_NONE before the first value; the bytes stay in the retained
+// input (argument a of batches[bid]).  Lock-free: a candidate that does not beat the current
+// winner is dropped (the winner only moves one way, so it never will); otherwise one CAS puts the
+// candidate's reference over the word, and a lost CAS hands back the word another lane installed,
+// which the loop compares against next.  No lane ever waits for a store another lane has yet to
+// make (there is no lock and no publish step), so the structurizer hazard at_minmax128 documents
+// cannot arise: whatever order the lanes of a wave leave the loop in, every iteration of every
+// lane either settles it or follows another lane's completed CAS.  Equal strings are
+// byte-identical, so a tie keeps the current reference.  The spin cap only guards a hang.
 template <int AS>
-__device__ __forceinline__ void apply_row(const Spec& S, wptr<AS> st, const BatchDesc& B, u64 i) {
+__device__ __forceinline__ void at_minmax_str(wptr<AS> w, u64 cand_ref, bool mn, const BatchDesc* batches, int a, u64* err) {
+    const StrRef c = dcol_str(batches[ref_bid(cand_ref)].args[a], ref_row(cand_ref));
+    u64 cur = __hip_atomic_load(w, __ATOMIC_RELAXED, AT_SCOPE(AS));
+    u32 spins = 0;
+    bool done = false;
+    do {
+        if (cur != STR_REF_NONE) {
+            const StrRef o = dcol_str(batches[ref_bid(cur)].args[a], ref_row(cur));
+            const int r = cmp3_bytes8(c.p, c.len, o.p, o.len);
+            done = mn ? r >= 0 : r <= 0;
+        }
+        if (!done) {
+            const u64 old = at_cas<AS>(w, cur, cand_ref);
+            done = old == cur;
+            cur = old;
+        }
+    } while (!done && ++spins < (1u << 20));
+    if (!done) __hip_atomic_fetch_or(err, (u64)ERR_MINMAX_SPIN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// accumulate_keys of every aggregate for input row i of batch bid (B = batches[bid]) into the slot
+// at st (word 0 = entry).  STR = false compiles the String MIN/MAX update out: for kernels whose
+// host-side eligibility rejects such specs (the fast integer-key kernel sits at its register
+// limit: with the update in, its non-COUNT instances spilled 224 bytes per lane against 64 / 0).
+template <int AS, bool STR = true>
+__device__ __forceinline__ void apply_row(const Spec& S, wptr<AS> st, const BatchDesc& B, u64 i, const BatchDesc* batches, u32 bid) {
     for (int a = 0; a < S.n_aggs; ++a) {
         const DAgg& A = S.aggs[a];
         const DCol& c = B.args[a];
@@ -61,7 +96,8 @@ __device__ __forceinline__ void apply_row(const Spec& S, wptr<AS> st, const Batc
             }
             case DBG_AGG_MIN: case DBG_AGG_MAX: {
                 bool mn = A.kind == DBG_AGG_MIN;
-                if (A.mmk == MMK_I128) at_minmax128<AS>(w, dcol_bits(c, i), dcol_hi(c, i), mn, S.err);
+                if (STR && A.mmk == MMK_STR) at_minmax_str<AS>(w, ((u64)bid << 32) | i, mn, batches, a, S.err);
+                else if (A.mmk == MMK_I128) at_minmax128<AS>(w, dcol_bits(c, i), dcol_hi(c, i), mn, S.err);
                 else if (A.mmk == MMK_I64) at_minmax<AS>(w, (u64)dcol_i64(c, i), mn, true);
                 else at_minmax<AS>(w, A.mmk == MMK_U64 ? dcol_bits(c, i) : f64_order_key(dcol_f64(c, i)), mn, false);
                 break;
@@ -77,9 +113,10 @@ __device__ __forceinline__ void apply_row(const Spec& S, wptr<AS> st, const Batc
 template <bool SC1, int RAS>
 __device__ __forceinline__ u64 rdw(const u64* p) { return SC1 ? ld_sc1(p) : *asp<RAS>(p); }
 
-// merge_states with the partial state's word w given by get(w) (memory or registers)
-template <int AS, typename G>
-__device__ __forceinline__ void apply_state_get(const Spec& S, wptr<AS> st, G get) {
+// merge_states with the partial state's word w given by get(w) (memory or registers); batches:
+// the handle's batch table (String MIN/MAX states are references into it)
+template <int AS, bool STR = true, typename G>
+__device__ __forceinline__ void apply_state_get(const Spec& S, wptr<AS> st, G get, const BatchDesc* batches) {
     for (int a = 0; a < S.n_aggs; ++a) {
         const DAgg& A = S.aggs[a];
         wptr<AS> w = st + A.w0;
@@ -99,7 +136,8 @@ __device__ __forceinline__ void apply_state_get(const Spec& S, wptr<AS> st, G ge
                 break;
             }
             case DBG_AGG_MIN: case DBG_AGG_MAX:
-                if (A.mmk == MMK_I128) at_minmax128<AS>(w, get(x + 1), get(x + 2), A.kind == DBG_AGG_MIN, S.err);
+                if (STR && A.mmk == MMK_STR) { if (x0 != STR_REF_NONE) at_minmax_str<AS>(w, x0, A.kind == DBG_AGG_MIN, batches, a, S.err); }
+                else if (A.mmk == MMK_I128) at_minmax128<AS>(w, get(x + 1), get(x + 2), A.kind == DBG_AGG_MIN, S.err);
                 else at_minmax<AS>(w, x0, A.kind == DBG_AGG_MIN, A.mmk == MMK_I64);
                 break;
         }
@@ -110,9 +148,9 @@ __device__ __forceinline__ void apply_state_get(const Spec& S, wptr<AS> st, G ge
     }
 }
 
-template <int AS, bool SC1 = false, int RAS = AS_GLB>
-__device__ __forceinline__ void apply_state(const Spec& S, wptr<AS> st, const u64* r) {
-    apply_state_get<AS>(S, st, [&](int w) { return rdw<SC1, RAS>(r + w); });
+template <int AS, bool SC1 = false, int RAS = AS_GLB, bool STR = true>
+__device__ __forceinline__ void apply_state(const Spec& S, wptr<AS> st, const u64* r, const BatchDesc* batches) {
+    apply_state_get<AS, STR>(S, st, [&](int w) { return rdw<SC1, RAS>(r + w); }, batches);
 }
 
 struct U128 {
@@ -348,11 +386,14 @@ __device__ __forceinline__ bool agg_result(const Spec& S, const DAgg& A, const u
         }
         case DBG_AGG_MIN: case DBG_AGG_MAX: {
             if (!valid) {
-                lo = hi = 0;
+                lo = A.mmk == MMK_STR ? STR_REF_NONE : 0;
+                hi = 0;
                 break;
             }
             u64 v = w[0];
-            if (A.mmk == MMK_I128) {
+            if (A.mmk == MMK_STR) {  // the reference itself: abi.hip's gather turns it into offsets and bytes
+                lo = v;
+            } else if (A.mmk == MMK_I128) {
                 lo = w[1];
                 hi = w[2];
             } else if (A.mmk == MMK_F64) {

@@ -291,6 +291,24 @@ __device__ __forceinline__ int cmp3_bytes(const u8* a, u64 la, const u8* b, u64 
     }
     return la < lb ? -1 : (la > lb ? 1 : 0);
 }
+// The same order, 8 bytes per step: the words big-endian compare as the bytes do.  Aligned loads
+// only, and only of words that hold a byte of the strings (load_u64_unaligned / load_partial), so
+// any start address and any length are fine.
+__device__ __forceinline__ int cmp3_bytes8(const u8* a, u64 la, const u8* b, u64 lb) {
+    const u64 n = la < lb ? la : lb;
+    u64 k = 0;
+    for (; k + 8 <= n; k += 8) {
+        const u64 x = load_u64_unaligned(a + k), y = load_u64_unaligned(b + k);
+        if (x != y) return __builtin_bswap64(x) < __builtin_bswap64(y) ? -1 : 1;
+    }
+    if (k < n) {
+        const u64 r = n - k;  // 1..7: the bytes past them are shifted out
+        const u64 x = __builtin_bswap64(load_partial(a + k, r)) >> (8 * (8 - r));
+        const u64 y = __builtin_bswap64(load_partial(b + k, r)) >> (8 * (8 - r));
+        if (x != y) return x < y ? -1 : 1;
+    }
+    return la < lb ? -1 : (la > lb ? 1 : 0);
+}
 __device__ __forceinline__ bool apply_cmp(int c, int o) {
     switch (c) {
         case DBG_CMP_EQ: return o == 0;
@@ -378,8 +396,10 @@ enum {
     MMK_I64 = 0,  // signed (ints, date, timestamp, Decimal128 with precision <= 18)
     MMK_U64 = 1,  // unsigned
     MMK_F64 = 2,  // OrderedFloat order via the monotone u64 transform
-    MMK_I128 = 3  // Decimal128 with precision > 18: [seq, lo, hi] under a seqlock (agg.hpp at_minmax128)
+    MMK_I128 = 3,  // Decimal128 with precision > 18: [seq, lo, hi] under a seqlock (agg.hpp at_minmax128)
+    MMK_STR = 4    // String: one word, (bid << 32) | row of the winning input row (agg_dev.hpp at_minmax_str)
 };
+#define STR_REF_NONE 0xFFFFFFFFFFFFFFFFULL  // MMK_STR identity: no value yet (a real reference has bits 48..63 clear)
 
 struct DAgg {
     int32_t kind;      // dbg_agg_kind
@@ -415,6 +435,7 @@ __device__ __forceinline__ double f64_from_order_key(u64 k) {
 }
 
 __host__ __device__ inline u64 state_init_word(const DAgg& a, int w) {
+    if ((a.kind == DBG_AGG_MIN || a.kind == DBG_AGG_MAX) && a.mmk == MMK_STR) return STR_REF_NONE;
     if ((a.kind == DBG_AGG_MIN || a.kind == DBG_AGG_MAX) && a.mmk == MMK_I128) {
         // identity: i128::MAX for MIN, i128::MIN for MAX; word 0 is the sequence counter
         if (w == 0) return 0ULL;

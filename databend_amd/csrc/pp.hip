@@ -1389,7 +1389,7 @@ __global__ void __launch_bounds__(PP_AGG_NT) pp_agg_kernel(const Spec* __restric
                 const int ls = pp_find(S, batches, slots, cap, sw, rk, pm, list, &nlist);
                 if (ls >= 0)
                     apply_state<AS_LDS, false, AS_GLB>(S, (wptr<AS_LDS>)(slots + (size_t)ls * sw + kw8),
-                                                       (const u64*)(rk.p + S.pp_kw) - 1);
+                                                       (const u64*)(rk.p + S.pp_kw) - 1, batches);
                 else
                     pp_store_rec(sout + (s0 + atomicAdd(&novf[1], 1u)) * rws, rk, rws);
             }

@@ -22,7 +22,7 @@ EXPORTED = [
     "dbg_agg_result", "dbg_agg_finalize_into", "dbg_agg_set_recycle", "dbg_agg_set_partition_keys", "dbg_agg_finalize_into_async", "dbg_agg_finalize_wait", "dbg_agg_record_width", "dbg_agg_partition", "dbg_agg_export_records",
     "dbg_agg_merge_records", "dbg_agg_export_fixed", "dbg_agg_capacity", "dbg_agg_merge_fixed", "dbg_filter_select", "dbg_take_fixed", "dbg_sort_limit_indices", "dbg_sort_limit_multi", "dbg_agg_compact", "dbg_agg_retained_bytes", "dbg_prof_enable", "dbg_prof_reset",
     "dbg_prof_get", "dbg_prof_marker", "dbg_datagen", "dbg_agg_set_strategy", "dbg_agg_get_strategy",
-    "dbg_agg_record_layout", "dbg_agg_set_host_staging",
+    "dbg_agg_record_layout", "dbg_agg_set_host_staging", "dbg_agg_result_string_bytes",
     "dbg_take_string", "dbg_legacy_hash_method", "dbg_legacy_group_hash", "dbg_agg_serialized_stride", "dbg_agg_result_serialized", "dbg_agg_merge_serialized", "dbg_comm_get_unique_id", "dbg_comm_create", "dbg_comm_destroy", "dbg_agg_exchange",
     "dbg_agg_payload_counts", "dbg_agg_payload_export", "dbg_agg_payload_import", "dbg_agg_exchange_payload",
     "dbg_payload_exchange_plan", "dbg_merge_exchange_plan", "dbg_agg_payload_counts_from", "dbg_agg_payload_export_from",
@@ -76,6 +76,7 @@ def lib():
         L.dbg_agg_add_groups.argtypes = [VP, P(abi.dbg_column), P(abi.dbg_column), P(abi.dbg_filter), U64, C.c_int]
         L.dbg_agg_finalize.argtypes = [VP, P(U64), P(U64)]
         L.dbg_agg_result.argtypes = [VP, P(abi.dbg_out_column), P(abi.dbg_out_column), C.c_int]
+        L.dbg_agg_result_string_bytes.argtypes = [VP, P(U64)]
         L.dbg_agg_finalize_into.argtypes = [VP, P(abi.dbg_out_column), P(abi.dbg_out_column), U64, P(U64), P(U64), P(U64)]
         L.dbg_agg_set_recycle.argtypes = [VP, C.c_int]
         L.dbg_agg_set_partition_keys.argtypes = [VP, C.c_int]

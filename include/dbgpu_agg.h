@@ -99,7 +99,7 @@ typedef struct dbg_out_column {
 typedef enum {
     DBG_AGG_COUNT = 0, /* AggregateCountFunction: count(*) when arg_type < 0, count(x) otherwise */
     DBG_AGG_SUM = 1,   /* NumberSumState / DecimalSumState<OVERFLOW> */
-    DBG_AGG_MIN = 2,   /* MinMaxAnyState<T, CmpMin> */
+    DBG_AGG_MIN = 2,   /* MinMaxAnyState<T, CmpMin>; T = String: see dbg_agg_result_string_bytes */
     DBG_AGG_MAX = 3,   /* MinMaxAnyState<T, CmpMax> */
     DBG_AGG_AVG = 4,   /* NumberAvgState / DecimalAvgState<OVERFLOW> */
     /* SQL avg(x): the planner rewrites it to sum(x) / if(count(x) = 0, 1, count(x))
@@ -204,6 +204,26 @@ int dbg_agg_finalize(dbg_agg_handle* h, uint64_t* n_groups, uint64_t* string_byt
 /* TransformFinalAggregate output DataBlock [agg results..., group cols...]
  * (AGG/transform_aggregate_final.rs:128-133): fills caller buffers (host when on_device == 0). */
 int dbg_agg_result(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_column* out_keys, int on_device);
+/* MIN / MAX of a String argument: MinMaxAnyState<StringType, CMP>
+ * (FUN/aggregate_min_max_any.rs:131-145; change_if of CmpMin / CmpMax,
+ * FUN/aggregate_scalar_state.rs:65-95), in &str order = unsigned bytewise lexicographic (a proper
+ * prefix sorts first, byte 0x80 above 0x7f).  The result column is a String: out_aggs[a] takes
+ * offsets (n_groups + 1), data and, when nullable, validity, in the group order of the keys; a
+ * group whose argument values are all NULL is NULL with length 0.
+ * After dbg_agg_finalize: payload bytes of each aggregate's result column (0 for non-String
+ * results), to size out_aggs[a].data.
+ *
+ * The state of such an aggregate is a reference to the winning input row, local to the handle, and
+ * the inputs of every batch stay retained until dbg_agg_reset.  A handle with one therefore runs
+ * the HBM table only and returns DBG_ERR_UNSUPPORTED from everything that ships, re-encodes or
+ * fuses states: dbg_agg_set_strategy(DBG_STRATEGY_PARTITIONED) (AUTO never switches),
+ * dbg_agg_partition / dbg_agg_export_records / dbg_agg_merge_records, dbg_agg_export_fixed /
+ * dbg_agg_merge_fixed, every dbg_agg_payload_* and dbg_agg_exchange* entry point and both
+ * exchange plans, dbg_agg_serialized_stride / dbg_agg_result_serialized /
+ * dbg_agg_merge_serialized, dbg_agg_record_layout, and dbg_agg_finalize_into(_async) (no room for
+ * the aggregates' string sizes).  dbg_agg_compact is a no-op (*compacted = 0).  The serialized
+ * form (borsh Option<String>) is not built yet. */
+int dbg_agg_result_string_bytes(dbg_agg_handle* h, uint64_t* agg_string_bytes /* n_aggs */);
 /* AggregateMeta::Serialized (AGG/aggregate_meta.rs:44-109; EAGG/payload_flush.rs:129-164): the
  * partial states as Binary columns, one per aggregate, + the group columns — what the reference
  * ships over Flight or spills, so a CPU final stage (or a GPU one) merges them.  Each row is the
