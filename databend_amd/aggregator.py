@@ -254,6 +254,14 @@ class AggregateHashTable:
         check(lib().dbg_agg_get_strategy(self.h, C.byref(p), C.byref(r)))
         return p.value == 2
 
+    def pp_stats(self):
+        """(final partition bits, final partitions handed to the generic kernel) of the last
+        partitioned finalize (dbg_agg_get_pp_stats).  A record's final partition is the top
+        `bits` bits of its group hash."""
+        b, s = C.c_uint32(), C.c_uint64()
+        check(lib().dbg_agg_get_pp_stats(self.h, C.byref(b), C.byref(s)))
+        return b.value, s.value
+
     # ---- AggregateHashTable::add_groups (+ fused filter)
     def add_groups(self, group_columns: Sequence[ColumnLike], params: Sequence[Optional[ColumnLike]],
                    rows: Optional[int] = None, filter_program=None, on_device: Optional[bool] = None) -> None:

@@ -1406,6 +1406,7 @@ static int pp_read_tot(dbg_agg_handle* h) {
     HIPCHECK(hipMemcpyAsync(h->pp_htot, h->pp_tot, PPT_WORDS * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     h->pp_stat_rounds = h->pp_htot[PPT_ROUNDS];
+    h->pp_stat_spilled = h->pp_htot[PPT_SPILLED];
     if (h->pp_htot[PPT_ERR] & ERR_OVF_LOST) return fail(DBG_ERR_INTERNAL, "partitioned aggregate: spill list exhausted");
     return DBG_OK;
 }
@@ -1947,6 +1948,13 @@ int dbg_agg_get_strategy(dbg_agg_handle* h, int* partitioned, uint64_t* extra_ro
     return DBG_OK;
 }
 
+int dbg_agg_get_pp_stats(dbg_agg_handle* h, uint32_t* final_bits, uint64_t* spilled_partitions) {
+    if (!h) return fail(DBG_ERR_INVALID, "null handle");
+    if (final_bits) *final_bits = h->pp_bits;
+    if (spilled_partitions) *spilled_partitions = h->pp_stat_spilled;
+    return DBG_OK;
+}
+
 int dbg_agg_set_partition_keys(dbg_agg_handle* h, int n_keys) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
     if (n_keys < 0 || n_keys > h->spec.n_keys) return fail(DBG_ERR_INVALID, "partition keys: 0..n_group_cols");
@@ -1988,6 +1996,7 @@ static int pp_fin_complete(dbg_agg_handle* h, uint64_t* n_groups, uint64_t* stri
     h->uploads_pending = false;
     const u64* t = h->pp_htot;
     h->pp_stat_rounds = t[PPT_ROUNDS];
+    h->pp_stat_spilled = t[PPT_SPILLED];
     h->n_groups = t[PPT_GROUPS];
     h->string_bytes.assign(S.n_keys, 0);
     bool short_buf = h->n_groups > F.max_groups;

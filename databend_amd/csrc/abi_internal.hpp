@@ -241,6 +241,7 @@ struct dbg_agg_handle {
     bool pp_grec_ready = false;
     u64 pp_nb = 0;            // blocks of the grec passes
     u64 pp_stat_rounds = 0;   // partitions that took more than one LDS round (last finalize)
+    u64 pp_stat_spilled = 0;  // final partitions handed to the generic kernel (last finalize)
     u64* ser_err = nullptr;   // serialized-state ingest error bits (serde.hip)
 
     // host-block staging (dbg_agg_set_host_staging, host_stage.hpp)

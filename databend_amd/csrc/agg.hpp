@@ -410,8 +410,10 @@ struct PPAggOut {
     u64* tot;       // PPT_* words (device)
     u64* trace;     // EXPERIMENT (DBG_X_PPTRACE): summed phase durations of sampled workgroups
 };
-// device totals of one partitioned finalize: groups, string bytes per key column, extra rounds, errors
-enum { PPT_GROUPS = 0, PPT_STR = 1, PPT_ROUNDS = 1 + DBG_MAX_KEYS, PPT_ERR = 2 + DBG_MAX_KEYS, PPT_WORDS = 4 + DBG_MAX_KEYS };
+// device totals of one partitioned finalize: groups, string bytes per key column, extra rounds, errors,
+// final partitions the specialised / record-centric kernel handed to the generic kernel
+enum { PPT_GROUPS = 0, PPT_STR = 1, PPT_ROUNDS = 1 + DBG_MAX_KEYS, PPT_ERR = 2 + DBG_MAX_KEYS, PPT_SPILLED = 3 + DBG_MAX_KEYS,
+       PPT_WORDS = 4 + DBG_MAX_KEYS };
 u32 pp_agg_slots(const Spec& hspec);
 struct CopyRange {
     u64 src, dst, n;  // byte offsets / length (multiples of 8)

@@ -1500,6 +1500,7 @@ __global__ void __launch_bounds__(PP_AGG_NT) pp_agg_rc_kernel(const Spec* __rest
     const u32 smask = (1u << sub_bits) - 1;
     auto spill_part = [&](u32 p) {
         const u32 k = atomicAdd(spill, 1u);
+        atomicAdd((unsigned long long*)(out.tot + PPT_SPILLED), 1ULL);
         if (k < spill_cap) spill[1 + k] = p;
         else atomicOr((unsigned long long*)(out.tot + PPT_ERR), (unsigned long long)ERR_OVF_LOST);
     };
@@ -1978,6 +1979,7 @@ __global__ void __launch_bounds__(SNT, SNT / 256) pp_agg_desc_kernel(const PsDes
         if (n > (u64)SNT * RPT) {  // uniform: the generic kernel takes it
             if (tid == 0) {
                 const u32 k = atomicAdd(spill, 1u);
+                atomicAdd((unsigned long long*)(out.tot + PPT_SPILLED), 1ULL);
                 if (k < spill_cap) spill[1 + k] = p;
                 else atomicOr((unsigned long long*)(out.tot + PPT_ERR), (unsigned long long)ERR_OVF_LOST);
             }
@@ -2521,6 +2523,7 @@ __global__ void __launch_bounds__(SNT, (SNT / 256) * PP_LIT_PER_CU) pp_agg_spec_
         if (n > (u64)SNT * RPT) {  // uniform: the generic kernel takes it
             if (tid == 0) {
                 const u32 k = atomicAdd(spill, 1u);
+                atomicAdd((unsigned long long*)(out.tot + PPT_SPILLED), 1ULL);
                 if (k < spill_cap) spill[1 + k] = p;
                 else atomicOr((unsigned long long*)(out.tot + PPT_ERR), (unsigned long long)ERR_OVF_LOST);
             }

@@ -328,6 +328,14 @@ int dbg_agg_set_strategy(dbg_agg_handle* h, int strategy);
  * whose last finalize ran the compile-time specialised aggregation); *extra_rounds (may be NULL) =
  * partitions of the last partitioned finalize whose groups needed more than one LDS round. */
 int dbg_agg_get_strategy(dbg_agg_handle* h, int* partitioned, uint64_t* extra_rounds);
+/* Read-only statistics of the last partitioned finalize (either pointer may be NULL).
+ * *final_bits = the number of hash bits that select a final partition: a record's final partition
+ * is the top *final_bits bits of its group hash (0 before the first partitioned finalize).
+ * *spilled_partitions = the final partitions that the specialised or record-centric aggregation
+ * found larger than its per-partition record budget and handed to the generic kernel (0 when
+ * neither ran).  Both are read from what the finalize already copied to the host: the call never
+ * touches the device. */
+int dbg_agg_get_pp_stats(dbg_agg_handle* h, uint32_t* final_bits, uint64_t* spilled_partitions);
 
 /* ---- partial-state records: exchange / partition bucket (EAGG/payload.rs:356-391,
  *      EAGG/partitioned_payload.rs:100-143, AGG/aggregate_exchange_injector.rs:154-235) ----

@@ -60,6 +60,7 @@ def gpu_aggregate(keys, aggs, filt=None, on_device=False, capacity_hint=0, batch
         if info is not None:
             info["partitioned"], info["extra_rounds"] = ht.strategy()
             info["specialised"] = ht.pp_specialised()
+            info["pp_bits"], info["spilled"] = ht.pp_stats()
     finally:
         ht.close()
     na = len(aggs)
