@@ -16,6 +16,7 @@ DBG_ERR_DEVICE = 6
 # dbg_type
 INT8, INT16, INT32, INT64, UINT8, UINT16, UINT32, UINT64 = range(8)
 FLOAT32, FLOAT64, DECIMAL128, DATE, TIMESTAMP, STRING, BOOLEAN = range(8, 15)
+DECIMAL256 = 15  # i256 LE: four u64 words, word 0 least significant
 
 # dbg_agg_kind
 AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_AVG, AGG_AVG_SQL = range(6)

@@ -71,7 +71,7 @@ class AggregatorParams:
 def _empty_column(t: DataType) -> Column:
     if t.type_id == abi.STRING:
         return Column(t, np.zeros(0, np.uint8), np.zeros(1, np.uint64), np.zeros(0, bool) if t.nullable else None)
-    if t.type_id == abi.DECIMAL128:
+    if t.type_id in (abi.DECIMAL128, abi.DECIMAL256):
         return Column(t, np.zeros(0, np.uint8), None, np.zeros(0, bool) if t.nullable else None)
     if t.type_id == abi.BOOLEAN:
         return Column(t, np.zeros(0, bool), None, np.zeros(0, bool) if t.nullable else None)
@@ -386,8 +386,8 @@ class AggregateHashTable:
         if t.type_id == abi.STRING:
             offs = b["offs"]
             data = b["data"][:int(offs[-1])]
-        elif t.type_id == abi.DECIMAL128:
-            data, offs = b["data"][:16 * n], None
+        elif t.type_id in (abi.DECIMAL128, abi.DECIMAL256):
+            data, offs = b["data"][:t.width * n], None
         elif t.type_id == abi.BOOLEAN:
             data, offs = b["data"][:n].astype(bool), None
         else:

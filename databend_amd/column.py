@@ -2,7 +2,8 @@
 
 Mirrors `DataType`, `Column`, `DataBlock` (src/query/expression/src/types/*, values.rs:157-176,
 block.rs:43-53) closely enough that a DataBlock can be handed across the C ABI without copies:
-fixed-width values are little-endian numpy buffers (Decimal128 = 16-byte i128 LE), strings are a
+fixed-width values are little-endian numpy buffers (Decimal128 = 16-byte i128 LE, Decimal256 =
+32-byte i256 LE, word 0 least significant: ethnum::i256's layout), strings are a
 byte buffer plus len+1 u64 offsets, validity is an arrow-style bitmap.  Device columns hold torch
 tensors (torch is plumbing for device memory only).
 """
@@ -10,7 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
-from decimal import Decimal
+from decimal import Context, Decimal
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -24,10 +25,11 @@ _NP = {
 }
 _WIDTH = {abi.INT8: 1, abi.INT16: 2, abi.INT32: 4, abi.INT64: 8, abi.UINT8: 1, abi.UINT16: 2,
           abi.UINT32: 4, abi.UINT64: 8, abi.FLOAT32: 4, abi.FLOAT64: 8, abi.DECIMAL128: 16,
-          abi.DATE: 4, abi.TIMESTAMP: 8, abi.BOOLEAN: 1}
+          abi.DECIMAL256: 32, abi.DATE: 4, abi.TIMESTAMP: 8, abi.BOOLEAN: 1}
 _NAMES = {abi.INT8: "Int8", abi.INT16: "Int16", abi.INT32: "Int32", abi.INT64: "Int64",
           abi.UINT8: "UInt8", abi.UINT16: "UInt16", abi.UINT32: "UInt32", abi.UINT64: "UInt64",
           abi.FLOAT32: "Float32", abi.FLOAT64: "Float64", abi.DECIMAL128: "Decimal",
+          abi.DECIMAL256: "Decimal",
           abi.DATE: "Date", abi.TIMESTAMP: "Timestamp", abi.STRING: "String",
           abi.BOOLEAN: "Boolean"}
 
@@ -66,7 +68,7 @@ class DataType:
 
     def __repr__(self) -> str:
         n = _NAMES.get(self.type_id, str(self.type_id))
-        if self.type_id == abi.DECIMAL128:
+        if self.type_id in (abi.DECIMAL128, abi.DECIMAL256):
             n = f"Decimal({self.precision}, {self.scale})"
         return f"Nullable({n})" if self.nullable else n
 
@@ -79,6 +81,22 @@ Date, Timestamp, String, Boolean = (DataType(t) for t in (abi.DATE, abi.TIMESTAM
 
 def Decimal128(precision: int, scale: int) -> DataType:
     return DataType(abi.DECIMAL128, precision, scale)
+
+
+def Decimal256(precision: int, scale: int) -> DataType:
+    return DataType(abi.DECIMAL256, precision, scale)
+
+
+MAX_DECIMAL128_PRECISION = 38
+MAX_DECIMAL256_PRECISION = 76
+
+
+def decimal_from_size(precision: int, scale: int) -> DataType:
+    """`DecimalDataType::from_size` (EXP/types/decimal.rs:903-921): Decimal128 up to 38 digits,
+    Decimal256 up to 76."""
+    if precision > MAX_DECIMAL256_PRECISION:
+        raise ValueError(f"Decimal({precision}, {scale}): precision above {MAX_DECIMAL256_PRECISION}")
+    return Decimal128(precision, scale) if precision <= MAX_DECIMAL128_PRECISION else Decimal256(precision, scale)
 
 
 def pack_bits(mask: np.ndarray) -> np.ndarray:
@@ -103,9 +121,21 @@ def i128_from_bytes(buf: np.ndarray) -> List[int]:
     return [int(h) * (1 << 64) + int(l) for l, h in zip(lo, hi)]
 
 
+def i256_to_bytes(values: Sequence[int]) -> np.ndarray:
+    out = np.zeros(len(values) * 32, dtype=np.uint8)
+    for i, v in enumerate(values):
+        out[i * 32:(i + 1) * 32] = np.frombuffer(int(v).to_bytes(32, "little", signed=True), dtype=np.uint8)
+    return out
+
+
+def i256_from_bytes(buf: np.ndarray) -> List[int]:
+    b = np.ascontiguousarray(np.asarray(buf, dtype=np.uint8)).reshape(-1, 32)
+    return [int.from_bytes(row.tobytes(), "little", signed=True) for row in b]
+
+
 @dataclass
 class Column:
-    """A host Column: `data` numpy buffer (uint8 bytes for String/Decimal128, typed otherwise),
+    """A host Column: `data` numpy buffer (uint8 bytes for String/Decimal128/Decimal256, typed otherwise),
     `offsets` (String), `validity` (bool per row, None = all valid)."""
     dtype: DataType
     data: np.ndarray
@@ -118,6 +148,8 @@ class Column:
             return len(self.offsets) - 1
         if self.dtype.type_id == abi.DECIMAL128:
             return len(self.data) // 16
+        if self.dtype.type_id == abi.DECIMAL256:
+            return len(self.data) // 32
         return len(self.data)
 
     # ---- constructors mirroring `XType::from_data` / `from_data_with_validity`
@@ -145,8 +177,9 @@ class Column:
             validity = [x is not None for x in values]
         ints = [0 if x is None else int(x) for x in values]
         v = None if validity is None else np.asarray(validity, dtype=bool)
-        dt = Decimal128(precision, scale)
-        return Column(dt.wrap_nullable() if v is not None else dt, i128_to_bytes(ints), None, v)
+        dt = decimal_from_size(precision, scale)  # Decimal256 above 38 digits
+        data = i256_to_bytes(ints) if dt.type_id == abi.DECIMAL256 else i128_to_bytes(ints)
+        return Column(dt.wrap_nullable() if v is not None else dt, data, None, v)
 
     @staticmethod
     def from_bools(values: Sequence, validity=None) -> "Column":
@@ -183,6 +216,8 @@ class Column:
             out = [bytes(self.data[int(self.offsets[i]):int(self.offsets[i + 1])]) for i in range(n)]
         elif t == abi.DECIMAL128:
             out = i128_from_bytes(self.data)
+        elif t == abi.DECIMAL256:
+            out = i256_from_bytes(self.data)
         elif t == abi.BOOLEAN:
             out = [bool(x) for x in self.data]
         elif t in (abi.FLOAT32, abi.FLOAT64):
@@ -195,6 +230,9 @@ class Column:
 
     def decimal_values(self) -> list:
         s = self.dtype.scale
+        if self.dtype.type_id == abi.DECIMAL256:  # up to 77 digits: past the default context's 28
+            ctx = Context(prec=80)
+            return [None if v is None else Decimal(v).scaleb(-s, context=ctx) for v in self.values()]
         return [None if v is None else Decimal(v).scaleb(-s) for v in self.values()]
 
 

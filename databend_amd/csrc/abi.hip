@@ -136,34 +136,53 @@ static int own_copy(dbg_agg_handle* h, const void* src, size_t bytes, const void
 static bool is_signed_i(int t) { return t == DBG_INT8 || t == DBG_INT16 || t == DBG_INT32 || t == DBG_INT64; }
 static bool is_unsigned_i(int t) { return t == DBG_UINT8 || t == DBG_UINT16 || t == DBG_UINT32 || t == DBG_UINT64; }
 static bool is_float(int t) { return t == DBG_FLOAT32 || t == DBG_FLOAT64; }
-static bool valid_type(int t) { return t >= DBG_INT8 && t <= DBG_BOOLEAN; }
+static bool valid_type(int t) { return t >= DBG_INT8 && t <= DBG_DECIMAL256; }
+// Decimal256 is what DecimalDataType::from_size gives for precision 39..76 (EXP/types/decimal.rs:903-921)
+static int check_decimal256(const dbg_datatype& t) {
+    if (t.type != DBG_DECIMAL256) return DBG_OK;
+    if (t.precision < 39 || t.precision > 76 || t.scale > t.precision)
+        return fail(DBG_ERR_INVALID, "Decimal256 needs precision 39..76 and scale <= precision");
+    return DBG_OK;
+}
+// Entry points outside the hash aggregate (filter predicates, take, sort, legacy hash methods)
+// carry values as at most two words: a Decimal256 column is refused, never read with a narrower width.
+#define REFUSE_DECIMAL256(t, what)                                                                           \
+    do {                                                                                                     \
+        if ((t) == DBG_DECIMAL256) return fail(DBG_ERR_UNSUPPORTED, std::string(what) + ": Decimal256 columns are not supported"); \
+    } while (0)
 
 // AggregateFunction::return_type() of the factory-built function.
 static int result_type_of(const dbg_agg_spec& s, dbg_datatype* out) {
     int t = s.arg.type;
     dbg_datatype r{DBG_UINT64, 0, 0, 0, 0};
     if (s.kind == DBG_AGG_COUNT) {
+        RETURN_IF(check_decimal256(s.arg));  // count(x): the argument's type is still declared
         *out = r;  // AggregateCountFunction: UInt64, never nullable
         return DBG_OK;
     }
     if (t < 0 || !valid_type(t)) return fail(DBG_ERR_INVALID, "aggregate needs an argument type");
+    RETURN_IF(check_decimal256(s.arg));
     switch (s.kind) {
         case DBG_AGG_SUM:  // ResultTypeOfUnary::Sum
             if (is_signed_i(t)) r.type = DBG_INT64;
             else if (is_unsigned_i(t)) r.type = DBG_UINT64;
             else if (is_float(t)) r.type = DBG_FLOAT64;
             else if (t == DBG_DECIMAL128) r = dbg_datatype{DBG_DECIMAL128, 38, s.arg.scale, 0, 0};
+            else if (t == DBG_DECIMAL256) r = dbg_datatype{DBG_DECIMAL256, 76, s.arg.scale, 0, 0};  // aggregate_sum.rs:224-250
             else return fail(DBG_ERR_UNSUPPORTED, "sum: unsupported argument type");
             break;
         case DBG_AGG_AVG:
             if (is_signed_i(t) || is_unsigned_i(t) || is_float(t)) r.type = DBG_FLOAT64;
             else if (t == DBG_DECIMAL128) r = dbg_datatype{DBG_DECIMAL128, 38, (uint8_t)std::max<int>(s.arg.scale, 4), 0, 0};
+            else if (t == DBG_DECIMAL256)  // aggregate_avg.rs:261-270
+                r = dbg_datatype{DBG_DECIMAL256, 76, (uint8_t)std::max<int>(s.arg.scale, 4), 0, 0};
             else return fail(DBG_ERR_UNSUPPORTED, "avg: unsupported argument type");
             break;
         case DBG_AGG_AVG_SQL:  // divide's result type (EXP/types/decimal.rs:1015-1037; numbers: Float64)
             if (is_signed_i(t) || is_unsigned_i(t) || is_float(t)) r.type = DBG_FLOAT64;
             else if (t == DBG_DECIMAL128)
                 r = dbg_datatype{DBG_DECIMAL128, 38, (uint8_t)std::max<int>(s.arg.scale, std::min<int>(s.arg.scale + 6, 12)), 0, 0};
+            else if (t == DBG_DECIMAL256) return fail(DBG_ERR_UNSUPPORTED, "avg (SQL) over Decimal256: the 256-bit rounding divide is not built");
             else return fail(DBG_ERR_UNSUPPORTED, "avg: unsupported argument type");
             break;
         case DBG_AGG_MIN: case DBG_AGG_MAX:
@@ -192,9 +211,10 @@ int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtyp
     for (int c = 0; c < S.n_keys; ++c) {
         dbg_datatype t = p->group_types[c];
         if (!valid_type(t.type)) return fail(DBG_ERR_INVALID, "bad group type");
+        RETURN_IF(check_decimal256(t));
         S.key_types[c] = t;
         if (t.type == DBG_STRING) S.has_strings = 1;
-        if (t.type == DBG_STRING || t.type == DBG_DECIMAL128) fixed = false;
+        if (t.type == DBG_STRING || t.type == DBG_DECIMAL128 || t.type == DBG_DECIMAL256) fixed = false;  // reference keys
         if (t.nullable) S.voff[c] = (uint8_t)w++;
     }
     for (int c = 0; c < S.n_keys; ++c) {
@@ -211,7 +231,7 @@ int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtyp
     for (int c = 0; c < S.n_keys; ++c) {
         S.rec_key_off[c] = off;
         int t = S.key_types[c].type;
-        off += (t == DBG_STRING || t == DBG_DECIMAL128) ? 16 : 8;
+        off += (t == DBG_STRING || t == DBG_DECIMAL128) ? 16 : 8;  // Decimal256: no record format (handle-local spec)
     }
     // state words
     int word = 1, flag_bits = 0;
@@ -227,16 +247,17 @@ int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtyp
         A.arg_type = s.kind == DBG_AGG_COUNT && s.arg.type < 0 ? -1 : s.arg.type;
         A.arg_nullable = A.arg_type >= 0 ? s.arg.nullable : 0;
         int t = A.arg_type;
-        A.sumk = t == DBG_DECIMAL128 ? SUMK_I128 : (is_float(t) ? SUMK_F64 : SUMK_I64);
+        A.sumk = t == DBG_DECIMAL256 ? SUMK_I256 : (t == DBG_DECIMAL128 ? SUMK_I128 : (is_float(t) ? SUMK_F64 : SUMK_I64));
         A.mmk = is_unsigned_i(t) ? MMK_U64 : (is_float(t) ? MMK_F64 : MMK_I64);
         if (t == DBG_DECIMAL128 && s.arg.precision > 18) A.mmk = MMK_I128;
+        if (t == DBG_DECIMAL256) A.mmk = MMK_I256;
         if (t == DBG_STRING && (s.kind == DBG_AGG_MIN || s.kind == DBG_AGG_MAX)) A.mmk = MMK_STR;
         A.w0 = word;
         switch (A.kind) {
             case DBG_AGG_COUNT: A.nwords = 1; break;
-            case DBG_AGG_SUM: A.nwords = A.sumk == SUMK_I128 ? 2 : 1; break;
-            case DBG_AGG_AVG: A.nwords = A.sumk == SUMK_I128 ? 3 : 2; break;
-            default: A.nwords = A.mmk == MMK_I128 ? 3 : 1;
+            case DBG_AGG_SUM: A.nwords = sum_words(A.sumk); break;
+            case DBG_AGG_AVG: A.nwords = sum_words(A.sumk) + 1; break;
+            default: A.nwords = A.mmk == MMK_I256 ? 5 : (A.mmk == MMK_I128 ? 3 : 1);
         }
         word += A.nwords;
         A.flag_bit = -1;
@@ -247,7 +268,7 @@ int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtyp
         A.res_nullable = rt.nullable;
         // SUM's range check (DecimalSumState<OVERFLOW>, p <= 18) also guards AVG_SQL's sum
         A.dec_check = ((s.kind == DBG_AGG_SUM || sql_avg) && t == DBG_DECIMAL128 && s.arg.precision <= 18) ? 1 : 0;
-        A.scale_add = (A.kind == DBG_AGG_AVG && t == DBG_DECIMAL128) ? (int)rt.scale - (int)s.arg.scale : 0;
+        A.scale_add = (A.kind == DBG_AGG_AVG && (t == DBG_DECIMAL128 || t == DBG_DECIMAL256)) ? (int)rt.scale - (int)s.arg.scale : 0;
         A.avg_round = sql_avg && t == DBG_DECIMAL128;
         A.res_width = (int)type_width(rt.type);
         if (is_str_minmax(A)) A.res_width = 8;  // the result writers emit the row reference; dbg_agg_result gathers the bytes
@@ -312,8 +333,8 @@ int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtyp
     if (!vbits) S.pp_avoff = S.pp_rw_raw;
     S.pp_rw_state = S.pp_kw + 8 * (u32)S.n_words;
     S.pp_sw = 1 + S.pp_kw / 8 + (u32)S.n_words;
-    // String MIN/MAX states are row references local to this handle's HBM table: never partitioned
-    S.pp_ok = S.pp_rw_raw <= 256 && S.pp_rw_state <= 256 && vbits <= 64 && S.pp_sw <= 64 && !has_str_minmax(S);
+    // a handle-local spec (String MIN/MAX row references, Decimal256 keys or arguments) is never partitioned
+    S.pp_ok = S.pp_rw_raw <= 256 && S.pp_rw_state <= 256 && vbits <= 64 && S.pp_sw <= 64 && !handle_local_reason(S);
     return DBG_OK;
 }
 
@@ -541,7 +562,7 @@ static int submit_batch(dbg_agg_handle* h, BatchDesc** pst, u32* pbid, bool cach
 static int to_dcol(dbg_agg_handle* h, const dbg_column& c, const dbg_datatype& want, bool check_type, int on_device, DCol& d) {
     memset(&d, 0, sizeof(d));
     if (!valid_type(c.dt.type)) return fail(DBG_ERR_INVALID, "bad column type");
-    if (check_type && (c.dt.type != want.type || (c.dt.type == DBG_DECIMAL128 && c.dt.scale != want.scale)))
+    if (check_type && (c.dt.type != want.type || ((c.dt.type == DBG_DECIMAL128 || c.dt.type == DBG_DECIMAL256) && c.dt.scale != want.scale)))
         return fail(DBG_ERR_INVALID, "column type does not match the declared type");
     if (check_type && c.dt.nullable && !want.nullable) return fail(DBG_ERR_INVALID, "nullable column for a non-nullable declared type");
     d.type = c.dt.type;
@@ -593,6 +614,8 @@ static int to_dcol(dbg_agg_handle* h, const dbg_column& c, const dbg_datatype& w
 
 static int fill_filter(dbg_agg_handle* h, const dbg_filter* f, int on_device, DCol* cols, int* ncols, DNode* nodes, int* nnodes) {
     if (f->n_cols > DBG_MAX_FCOLS || f->n_nodes > DBG_MAX_NODES) return fail(DBG_ERR_UNSUPPORTED, "filter too large");
+    // predicates compare at most two words (cmp3_i128): no Decimal256 filter columns
+    for (int c = 0; c < f->n_cols; ++c) REFUSE_DECIMAL256(f->cols[c].dt.type, "filter");
     int depth = 0;
     for (int k = 0; k < f->n_nodes; ++k) {
         const dbg_pred_node& n = f->nodes[k];
@@ -1412,11 +1435,11 @@ static int pp_read_tot(dbg_agg_handle* h) {
 }
 
 // dbg_agg_finalize in partitioned mode: group records built, sizes known.
-// Decimal128 MIN/MAX (precision > 18) states are the only updates that can give up
-// (at_minmax128); handles without them skip the read-back.
+// Decimal128 (precision > 18) and Decimal256 MIN/MAX states are the only updates that can give up
+// (at_minmax128 / at_minmax256); handles without them skip the read-back.
 static int check_minmax_spin(dbg_agg_handle* h) {
     bool any = false;
-    for (int a = 0; a < h->spec.n_aggs; ++a) any |= h->spec.aggs[a].mmk == MMK_I128 &&
+    for (int a = 0; a < h->spec.n_aggs; ++a) any |= (h->spec.aggs[a].mmk == MMK_I128 || h->spec.aggs[a].mmk == MMK_I256) &&
                                                     (h->spec.aggs[a].kind == DBG_AGG_MIN || h->spec.aggs[a].kind == DBG_AGG_MAX);
     if (!any) return DBG_OK;
     u64 e = 0;
@@ -1708,7 +1731,7 @@ int dbg_agg_result(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_column* 
 
 int dbg_agg_serialized_stride(dbg_agg_handle* h, uint32_t* stride) {
     if (!h || !stride) return fail(DBG_ERR_INVALID, "null argument");
-    REFUSE_STR_MINMAX(h, "dbg_agg_serialized_stride");
+    REFUSE_HANDLE_LOCAL(h, "dbg_agg_serialized_stride");
     for (int a = 0; a < h->spec.n_aggs; ++a) {
         if (h->src_kinds[a] == DBG_AGG_AVG_SQL)
             return fail(DBG_ERR_UNSUPPORTED, "serialized states: SQL avg is sum and count in the reference plan");
@@ -1719,7 +1742,7 @@ int dbg_agg_serialized_stride(dbg_agg_handle* h, uint32_t* stride) {
 
 int dbg_agg_result_serialized(dbg_agg_handle* h, dbg_out_column* out_states, dbg_out_column* out_keys, int on_device) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
-    REFUSE_STR_MINMAX(h, "dbg_agg_result_serialized");
+    REFUSE_HANDLE_LOCAL(h, "dbg_agg_result_serialized");
     for (int a = 0; a < h->spec.n_aggs; ++a)
         if (h->src_kinds[a] == DBG_AGG_AVG_SQL)
             return fail(DBG_ERR_UNSUPPORTED, "serialized states: SQL avg is sum and count in the reference plan");
@@ -1924,7 +1947,7 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
 int dbg_agg_set_strategy(dbg_agg_handle* h, int strategy) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
     if (strategy < DBG_STRATEGY_AUTO || strategy > DBG_STRATEGY_PARTITIONED) return fail(DBG_ERR_INVALID, "unknown strategy");
-    if (strategy == DBG_STRATEGY_PARTITIONED) REFUSE_STR_MINMAX(h, "dbg_agg_set_strategy(PARTITIONED)");
+    if (strategy == DBG_STRATEGY_PARTITIONED) REFUSE_HANDLE_LOCAL(h, "dbg_agg_set_strategy(PARTITIONED)");
     if (h->table_rows || h->ppk[0].l1_n || h->ppk[1].l1_n)
         return fail(DBG_ERR_INVALID, "dbg_agg_set_strategy: the handle holds groups (call it after create or reset)");
     // AUTO switches only for records of <= 256 bytes (build_spec: pp_ok); a forced partitioned
@@ -2310,7 +2333,10 @@ int dbg_agg_finalize_into(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_c
 int dbg_agg_finalize_into_async(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_column* out_keys, uint64_t max_groups,
                                 const uint64_t* max_string_bytes) {
     if (!h || !out_aggs || !out_keys) return fail(DBG_ERR_INVALID, "null argument");
-    REFUSE_STR_MINMAX(h, "dbg_agg_finalize_into_async");
+    // String MIN/MAX: no room for the aggregates' string sizes.  Decimal256 results go through the
+    // same writers as dbg_agg_result, so that handle-local spec is served here.
+    if (has_str_minmax(h->spec))
+        return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_agg_finalize_into_async: ") + handle_local_reason(h->spec));
     if (h->fin.active) return fail(DBG_ERR_INVALID, "a finalize is already in flight: dbg_agg_finalize_wait first");
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(fin_setup(h, out_aggs, out_keys, max_groups, max_string_bytes));
@@ -2343,7 +2369,7 @@ int dbg_agg_record_layout(const dbg_agg_params* params, dbg_record_layout* out) 
     Spec S;
     std::vector<dbg_datatype> rt;
     RETURN_IF(build_spec(params, S, rt));
-    if (has_str_minmax(S)) return fail(DBG_ERR_UNSUPPORTED, "dbg_agg_record_layout: String min/max states are row references local to a handle");
+    if (const char* why = handle_local_reason(S)) return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_agg_record_layout: ") + why);
     memset(out, 0, sizeof(*out));
     out->width = S.rec_width;
     out->state_off = S.rec_state_off;
@@ -2396,7 +2422,7 @@ static int legacy_layout(const Spec& S, u32 bits, LegacyLayout* L) {
 
 int dbg_agg_partition(dbg_agg_handle* h, uint32_t n_parts, int scheme, uint64_t* rec_counts, uint64_t* string_bytes) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
-    REFUSE_STR_MINMAX(h, "dbg_agg_partition");
+    REFUSE_HANDLE_LOCAL(h, "dbg_agg_partition");
     if (n_parts < 1 || n_parts > 256) return fail(DBG_ERR_UNSUPPORTED, "1..256 partitions");
     if (scheme < 0 || scheme > 2) return fail(DBG_ERR_INVALID, "scheme 0 (hash % n), 1 (radix bits) or 2 (legacy buckets)");
     if (scheme >= 1 && (n_parts & (n_parts - 1))) return fail(DBG_ERR_INVALID, "radix partitions must be a power of two");
@@ -2468,7 +2494,7 @@ int dbg_agg_partition(dbg_agg_handle* h, uint32_t n_parts, int scheme, uint64_t*
 
 int dbg_agg_export_records(dbg_agg_handle* h, void* dev_records, void* dev_strings) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
-    REFUSE_STR_MINMAX(h, "dbg_agg_export_records");
+    REFUSE_HANDLE_LOCAL(h, "dbg_agg_export_records");
     if (!h->part_n) return fail(DBG_ERR_INVALID, "dbg_agg_partition must precede dbg_agg_export_records");
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(flush_pending(h));
@@ -2493,7 +2519,7 @@ int dbg_agg_capacity(dbg_agg_handle* h, uint64_t* slots) {
 // ---- fixed-capacity exchange (replicas + gather, low cardinality) ----
 int dbg_agg_export_fixed(dbg_agg_handle* h, void* dev_buf, uint64_t cap_records) {
     if (!h || !dev_buf) return fail(DBG_ERR_INVALID, "null argument");
-    REFUSE_STR_MINMAX(h, "dbg_agg_export_fixed");
+    REFUSE_HANDLE_LOCAL(h, "dbg_agg_export_fixed");
     const Spec& S = h->spec;
     if (!S.inline_keys) return fail(DBG_ERR_UNSUPPORTED, "fixed export needs fixed-width (inline) group keys");
     if (h->cap + 1 > FIN_SMALL_SLOTS || h->pp) return fail(DBG_ERR_UNSUPPORTED, "fixed export is for small tables");
@@ -2514,7 +2540,7 @@ int dbg_agg_export_fixed(dbg_agg_handle* h, void* dev_buf, uint64_t cap_records)
 
 int dbg_agg_merge_fixed(dbg_agg_handle* h, const void* dev_bufs, int32_t n_bufs, uint64_t cap_records) {
     if (!h || !dev_bufs || n_bufs < 1) return fail(DBG_ERR_INVALID, "bad argument");
-    REFUSE_STR_MINMAX(h, "dbg_agg_merge_fixed");
+    REFUSE_HANDLE_LOCAL(h, "dbg_agg_merge_fixed");
     const Spec& S = h->spec;
     if (!S.inline_keys) return fail(DBG_ERR_UNSUPPORTED, "fixed merge needs fixed-width (inline) group keys");
     if (h->pp) return fail(DBG_ERR_UNSUPPORTED, "fixed merge: the handle runs partitioned (high cardinality)");
@@ -2598,7 +2624,7 @@ static int merge_record_batch(dbg_agg_handle* h, const u8* base, u64 n, const u8
 int dbg_agg_merge_records(dbg_agg_handle* h, const void* dev_records, const void* dev_strings, int32_t n_segments,
                           const uint64_t* seg_records, const uint64_t* seg_string_bytes) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
-    REFUSE_STR_MINMAX(h, "dbg_agg_merge_records");
+    REFUSE_HANDLE_LOCAL(h, "dbg_agg_merge_records");
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(flush_pending(h));
     h->finalized = false;
@@ -2631,8 +2657,9 @@ int dbg_agg_compact(dbg_agg_handle* h, int* compacted) {
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(flush_pending(h));
     const Spec& S = h->spec;
-    // String MIN/MAX states point into the retained input: nothing can be released (a no-op)
-    if (h->pp || S.inline_keys || has_str_minmax(S)) return DBG_OK;
+    // a handle-local spec (String MIN/MAX states point into the retained input; Decimal256 has no
+    // record format to re-merge from): nothing can be released (a no-op)
+    if (h->pp || S.inline_keys || handle_local_reason(S)) return DBG_OK;
     u64 n = 0, sb = 0;
     RETURN_IF(dbg_agg_partition(h, 1, 0, &n, &sb));
     DevBuf rb, strb;
@@ -2680,7 +2707,7 @@ int dbg_agg_retained_bytes(dbg_agg_handle* h, uint64_t* bytes) {
 int dbg_agg_merge_serialized(dbg_agg_handle* h, const dbg_column* state_cols, const dbg_column* group_cols, uint64_t rows,
                              int on_device) {
     if (!h || (!state_cols && h->spec.n_aggs) || !group_cols) return fail(DBG_ERR_INVALID, "null argument");
-    REFUSE_STR_MINMAX(h, "dbg_agg_merge_serialized");
+    REFUSE_HANDLE_LOCAL(h, "dbg_agg_merge_serialized");
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(flush_pending(h));
     h->finalized = false;
@@ -2770,6 +2797,7 @@ int dbg_filter_select(const dbg_filter* filter, uint64_t rows, uint32_t* sel_out
 int dbg_take_fixed(const dbg_column* col, const uint32_t* sel, uint64_t n_sel, void* out_data, uint8_t* out_validity, void* stream) {
     if (!col || !sel || !out_data) return fail(DBG_ERR_INVALID, "null argument");
     if (col->dt.type == DBG_STRING) return fail(DBG_ERR_UNSUPPORTED, "dbg_take_fixed: fixed-width columns only");
+    REFUSE_DECIMAL256(col->dt.type, "dbg_take_fixed");
     hipStream_t s = (hipStream_t)stream;
     DCol d;
     memset(&d, 0, sizeof(d));
@@ -2836,6 +2864,7 @@ static int legacy_method(const dbg_datatype* types, int n, int* kind, uint32_t* 
         *key_bytes = 0;
         return DBG_OK;
     }
+    for (int j = 0; j < n; ++j) REFUSE_DECIMAL256(types[j].type, "legacy hash methods");
     u32 len = 0;
     for (int j = 0; j < n; ++j) {
         const int t = types[j].type;
@@ -2924,6 +2953,7 @@ int dbg_sort_limit_indices(const dbg_column* col, uint64_t rows, int asc, int nu
                            uint32_t* idx_out, uint64_t* n_out, void* stream) {
     if (!col || !n_out || (!idx_out && limit && rows)) return fail(DBG_ERR_INVALID, "null argument");
     const int t = col->dt.type;
+    REFUSE_DECIMAL256(t, "dbg_sort_limit_indices");
     if (t == DBG_STRING || t == DBG_DECIMAL128 || type_width(t) == 0)
         return fail(DBG_ERR_UNSUPPORTED, "dbg_sort_limit_indices: fixed-width number columns only");
     DCol d;
@@ -2951,6 +2981,7 @@ int dbg_sort_limit_multi(const dbg_column* cols, int n_cols, const int* asc, con
     for (int c = 0; c < n_cols; ++c) {
         const dbg_column& col = cols[c];
         const int t = col.dt.type;
+        REFUSE_DECIMAL256(t, "dbg_sort_limit_multi");
         if (!valid_type(t) || (t != DBG_STRING && type_width(t) == 0))
             return fail(DBG_ERR_UNSUPPORTED, "dbg_sort_limit_multi: number, Decimal128 and String columns");
         if (col.len < rows) return fail(DBG_ERR_INVALID, "column shorter than rows");

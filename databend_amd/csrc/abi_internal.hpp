@@ -248,19 +248,34 @@ struct dbg_agg_handle {
     hstage::Stage stage;
 };
 
-// String MIN/MAX (MMK_STR): the state is a reference into this handle's retained input, so every
-// entry point that ships, re-encodes or compacts states refuses such a handle (REFUSE_STR_MINMAX)
+// Handle-local specs.  Records, the partitioned payload, the exchanges and the serialized states
+// carry keys and states of at most 16 bytes, and a String MIN/MAX state (MMK_STR) is a reference
+// into this handle's retained input.  A spec with a String MIN/MAX, or with a Decimal256 key or
+// argument, therefore runs the HBM table of its own handle only: every entry point that ships,
+// re-encodes or compacts states refuses it (REFUSE_HANDLE_LOCAL) with the reason given here.
 inline bool is_str_minmax(const DAgg& A) { return (A.kind == DBG_AGG_MIN || A.kind == DBG_AGG_MAX) && A.mmk == MMK_STR; }
 inline bool has_str_minmax(const Spec& S) {
     for (int a = 0; a < S.n_aggs; ++a)
         if (is_str_minmax(S.aggs[a])) return true;
     return false;
 }
-#define REFUSE_STR_MINMAX(h, what)                                                                              \
-    do {                                                                                                        \
-        if (has_str_minmax((h)->spec))                                                                          \
-            return fail(DBG_ERR_UNSUPPORTED, std::string(what) + ": String min/max states are row references " \
-                                                                 "local to the handle (dbg_agg_result only)"); \
+inline bool has_decimal256(const Spec& S) {
+    for (int c = 0; c < S.n_keys; ++c)
+        if (S.key_types[c].type == DBG_DECIMAL256) return true;
+    for (int a = 0; a < S.n_aggs; ++a)
+        if (S.aggs[a].arg_type == DBG_DECIMAL256) return true;
+    return false;
+}
+// nullptr: the spec's states and keys can leave the handle
+inline const char* handle_local_reason(const Spec& S) {
+    if (has_str_minmax(S)) return "String min/max states are row references local to the handle (dbg_agg_result only)";
+    if (has_decimal256(S)) return "Decimal256 keys and states are wider than the record formats (the HBM table of one handle only)";
+    return nullptr;
+}
+#define REFUSE_HANDLE_LOCAL(h, what)                                                          \
+    do {                                                                                      \
+        if (const char* why_ = handle_local_reason((h)->spec))                                \
+            return fail(DBG_ERR_UNSUPPORTED, std::string(what) + ": " + why_);               \
     } while (0)
 
 // handle helpers abi.hip defines for the other units

@@ -200,7 +200,7 @@ __device__ __forceinline__ u64 lds_entry_hash(const Spec& S, const BatchDesc& B,
     return group_hash(B.keys, S.n_keys, ref_row(e));
 }
 
-template <bool INLINE, bool RECORDS, bool STR = true>  // STR: see apply_row
+template <bool INLINE, bool RECORDS, bool STR = true, bool W256 = true>  // STR, W256: see apply_row
 __device__ __forceinline__ void flush_lds_direct(const Spec& S, const BatchDesc* batches, const BatchDesc& B, u64* lds,
                                                  u32 lds_slots, u32 sw, u32 nt, const TableDesc& t, u32& my_claims) {
     for (u32 s = threadIdx.x; s < lds_slots; s += nt) {
@@ -215,10 +215,11 @@ __device__ __forceinline__ void flush_lds_direct(const Spec& S, const BatchDesc*
             continue;
         }
         my_claims += claimed ? 1 : 0;
-        apply_state<AS_GLB, false, AS_LDS, STR>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), p, batches);
+        apply_state<AS_GLB, false, AS_LDS, STR, W256>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), p, batches);
     }
 }
 
+template <bool W256 = true>  // see apply_row
 __device__ __forceinline__ void lds_table_init(const Spec& S, u64* lds, u32 lds_slots, u32 sw, u32 nt) {
     for (u32 s = threadIdx.x; s < lds_slots; s += nt) {
         u64* p = lds + (u64)s * sw;
@@ -226,13 +227,13 @@ __device__ __forceinline__ void lds_table_init(const Spec& S, u64* lds, u32 lds_
         for (u32 w = 1; w < sw; ++w) p[w] = 0;
         for (int a = 0; a < S.n_aggs; ++a)
             if (S.aggs[a].kind == DBG_AGG_MIN || S.aggs[a].kind == DBG_AGG_MAX)
-                for (int k = 0; k < S.aggs[a].nwords; ++k) p[S.aggs[a].w0 + k] = state_init_word(S.aggs[a], k);
+                for (int k = 0; k < S.aggs[a].nwords; ++k) p[S.aggs[a].w0 + k] = state_init_word<W256>(S.aggs[a], k);
     }
 }
 
 // lcount: [0] LDS claims, [1] HBM claims, [2] parked entries, [3] last-workgroup flag.
 // Ends with the workgroup's HBM claims added to the table counter.
-template <bool INLINE, bool RECORDS, bool STR = true>
+template <bool INLINE, bool RECORDS, bool STR = true, bool W256 = true>
 __device__ __forceinline__ void block_flush(const Spec& S, const BatchDesc* batches, const BatchDesc& B, u64* lds, u32 lds_slots, u32 sw,
                             u32* lcount, u32 nt, const TableDesc& t, u32 my_claims) {
     const u32 lmask = lds_slots - 1;
@@ -255,7 +256,7 @@ __device__ __forceinline__ void block_flush(const Spec& S, const BatchDesc* batc
             if (threadIdx.x == 0) st_sc1(counts + blockIdx.x, lcount[2]);
         } else {
             if (threadIdx.x == 0) st_sc1(counts + blockIdx.x, 0);
-            flush_lds_direct<INLINE, RECORDS, STR>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
+            flush_lds_direct<INLINE, RECORDS, STR, W256>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
         }
         // Hand-off without release fences (MI355X_MICROARCH.md, inter-workgroup visibility, valid
         // forms): parked words are stored sc1 (write-through past the XCD's L2); every storing
@@ -280,7 +281,7 @@ __device__ __forceinline__ void block_flush(const Spec& S, const BatchDesc* batc
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 tickets[g] = 0;  // ready for the next launch on this table (all members have added)
             }
-            lds_table_init(S, lds, lds_slots, sw, nt);
+            lds_table_init<W256>(S, lds, lds_slots, sw, nt);
             if (threadIdx.x == 0) lcount[0] = 0;
             __syncthreads();
             const u32 total = gsize * SCR_ENTRIES;
@@ -293,7 +294,7 @@ __device__ __forceinline__ void block_flush(const Spec& S, const BatchDesc* batc
                 u64 h = lds_entry_hash<INLINE, RECORDS>(S, B, e);
                 int ls = lds_find<INLINE>(S, batches, B.keys, INLINE ? 0 : ref_row(e), e, h, lds, lmask, sw, lcount, llimit);
                 if (ls >= 0) {
-                    apply_state<AS_LDS, true, AS_GLB, STR>(S, asp<AS_LDS>(lds + (u64)ls * sw), r, batches);
+                    apply_state<AS_LDS, true, AS_GLB, STR, W256>(S, asp<AS_LDS>(lds + (u64)ls * sw), r, batches);
                     continue;
                 }
                 bool claimed;
@@ -303,13 +304,13 @@ __device__ __forceinline__ void block_flush(const Spec& S, const BatchDesc* batc
                     continue;
                 }
                 my_claims += claimed ? 1 : 0;
-                apply_state<AS_GLB, true, AS_GLB, STR>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), r, batches);
+                apply_state<AS_GLB, true, AS_GLB, STR, W256>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), r, batches);
             }
             __syncthreads();
-            flush_lds_direct<INLINE, RECORDS, STR>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
+            flush_lds_direct<INLINE, RECORDS, STR, W256>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
         }
     } else {
-        flush_lds_direct<INLINE, RECORDS, STR>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
+        flush_lds_direct<INLINE, RECORDS, STR, W256>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
     }
     if (my_claims) atomicAdd(&lcount[1], my_claims);
     __syncthreads();
@@ -1023,7 +1024,7 @@ __device__ __forceinline__ void short_tree_flush(const Spec& S, const BatchDesc*
         const bool direct = root || lcount[4] != 0 || lcount[5] > SCR_ENTRIES;
         const u64 b = (u64)node << shift;  // this node's scratch row
         if (direct) {
-            flush_lds_direct<false, false>(S, batches, B, lds, lds_slots, sw, BLOCK, t, my_claims);
+            flush_lds_direct<false, false, true, false>(S, batches, B, lds, lds_slots, sw, BLOCK, t, my_claims);
             if (!root && threadIdx.x == 0) st_sc1(counts + b, 0);
         } else {
             if (threadIdx.x == 0) lcount[2] = 0;
@@ -1058,7 +1059,7 @@ __device__ __forceinline__ void short_tree_flush(const Spec& S, const BatchDesc*
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             tickets[toff + g] = 0;  // ready for the next launch (all members have added)
         }
-        lds_table_init(S, lds, lds_slots, sw, BLOCK);
+        lds_table_init<false>(S, lds, lds_slots, sw, BLOCK);
         for (u32 j = threadIdx.x; j < lds_slots; j += BLOCK) pk0[j] = pk1[j] = PK_NONE;
         if (threadIdx.x == 0) lcount[0] = 0;
         __syncthreads();
@@ -1093,7 +1094,7 @@ __device__ __forceinline__ void short_tree_flush(const Spec& S, const BatchDesc*
                 pos = (pos + 1) & lmask;
             }
             if (ls >= 0) {
-                apply_state<AS_LDS, true>(S, asp<AS_LDS>(lds + (u64)ls * sw), r, batches);
+                apply_state<AS_LDS, true, AS_GLB, true, false>(S, asp<AS_LDS>(lds + (u64)ls * sw), r, batches);
                 continue;
             }
             // the merge table is full: this row goes to HBM by itself
@@ -1105,7 +1106,7 @@ __device__ __forceinline__ void short_tree_flush(const Spec& S, const BatchDesc*
                 continue;
             }
             my_claims += claimed ? 1 : 0;
-            apply_state<AS_GLB, true>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), r, batches);
+            apply_state<AS_GLB, true, AS_GLB, true, false>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), r, batches);
         }
         __syncthreads();
         toff += (n_nodes + SHORT_FANIN - 1) / SHORT_FANIN;
@@ -1140,7 +1141,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6)))
     u64* pk1 = pk0 + lds_slots;
     const u32 lmask = lds_slots - 1;
     const u32 llimit = lds_slots - lds_slots / 4;
-    lds_table_init(S, lds, lds_slots, sw, BLOCK);
+    lds_table_init<false>(S, lds, lds_slots, sw, BLOCK);
     for (u32 j = threadIdx.x; j < lds_slots; j += BLOCK) pk0[j] = pk1[j] = PK_NONE;
     if (threadIdx.x < 8) lcount[threadIdx.x] = 0;
     __syncthreads();
@@ -1197,7 +1198,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6)))
             s = (s + 1) & lmask;
         }
         if (ls >= 0) {
-            apply_row<AS_LDS>(S, asp<AS_LDS>(lds + (u64)ls * sw), B, i, batches, bid);
+            apply_row<AS_LDS, true, false>(S, asp<AS_LDS>(lds + (u64)ls * sw), B, i, batches, bid);  // no Decimal256 (short_eligible)
             return;
         }
         bool claimed;
@@ -1207,7 +1208,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6)))
             return;
         }
         my_claims += claimed ? 1 : 0;
-        apply_row<AS_GLB>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), B, i, batches, bid);
+        apply_row<AS_GLB, true, false>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), B, i, batches, bid);
     };
     auto process = [&](u64 i, const ShortRow& r) __attribute__((always_inline)) {
         const u64 l0 = r.o[1] - r.o[0], l1 = r.o[3] - r.o[2];
@@ -1326,7 +1327,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6)))
     const bool tree = tree_ok && t.scratch != nullptr && gridDim.x > 1 && gridDim.x <= t.scr_blocks;  // uniform
     tmark(3, true);
     if (tree) short_tree_flush(S, batches, B, lds, lds_slots, sw, lcount, pk0, pk1, t, my_claims);
-    else block_flush<false, false>(S, batches, B, lds, lds_slots, sw, lcount, BLOCK, t, my_claims);
+    else block_flush<false, false, true, false>(S, batches, B, lds, lds_slots, sw, lcount, BLOCK, t, my_claims);
     tmark(4, true);
 }
 
@@ -1339,6 +1340,7 @@ static bool short_eligible(const Spec& S, const BatchDesc& hb) {
         const DAgg& A = S.aggs[a];
         if (A.kind != DBG_AGG_COUNT && A.kind != DBG_AGG_SUM && A.kind != DBG_AGG_AVG) return false;
         if (A.arg_type >= 0 && A.arg_nullable) return false;
+        if (A.arg_type == DBG_DECIMAL256) return false;  // compiled without the 256-bit updates: the generic insert
     }
     return true;
 }
@@ -1673,6 +1675,7 @@ void launch_exclusive_scan(hipStream_t s, u64* data, u64 n, u64* total) {
 
 // flush_column of one group (slot s, entry e, state words st) into output row p; sp[c] = string
 // write cursor of key column c (advanced).
+template <bool W256 = true>  // see write_agg
 __device__ __forceinline__ void write_group(const Spec& S, const BatchDesc* batches, const TableDesc& t, u64 s, const u64* st,
                                            u64 e, u64 p, u64* sp, const OutDesc& out) {
     // group columns
@@ -1717,12 +1720,11 @@ __device__ __forceinline__ void write_group(const Spec& S, const BatchDesc* batc
                 }
                 sp[c] += r.len;
             } else {
-                u32 w = type_width(kc.type);
-                write_bytes(out.key_data[c], p, w, dcol_bits(kc, row), w == 16 ? dcol_hi(kc, row) : 0);
+                write_key_cell(out.key_data[c], p, kc, row);
             }
         }
     }
-    for (int a = 0; a < S.n_aggs; ++a) write_agg(S, a, st, p, out, t.counters + CNT_ERR);
+    for (int a = 0; a < S.n_aggs; ++a) write_agg<W256>(S, a, st, p, out, t.counters + CNT_ERR);
 }
 
 // Slot order within the block: iteration k covers slots base + k*BLOCK + tid (coalesced entry
@@ -1816,7 +1818,7 @@ __global__ void __launch_bounds__(BLOCK) write_results_kernel(const Spec* __rest
 // The body, run by FIN_NT threads of one workgroup: the standalone kernel below, or the last
 // workgroup of a fused insert (agg_insert_fast with FusedFin::on).  `view` holds the slots to
 // read (t.slots, or a copy in LDS); the re-initialisation of a recycled table writes t.slots.
-template <int MAXPER>
+template <int MAXPER, bool W256 = true>
 __device__ __forceinline__ bool finalize_small_body(const Spec& S, const BatchDesc* batches, const TableDesc& t, const u64* view,
                                                     const OutDesc& out, u64* totals, u64* host_mirror, int recycle, u64 seq,
                                                     u64* trace = nullptr, bool writeback = false, int xfin = 0) {
@@ -1836,7 +1838,7 @@ __device__ __forceinline__ bool finalize_small_body(const Spec& S, const BatchDe
     for (int c = 0; c < S.n_keys; ++c) has_bits |= out.key_valid[c] && out.key_bits[c];
     for (int a = 0; a < S.n_aggs; ++a) {
         has_bits |= (out.agg_valid[a] || ((out.all_valid >> a) & 1)) && out.agg_bits[a];
-        dec_err |= S.aggs[a].dec_check || (S.aggs[a].kind == DBG_AGG_AVG && S.aggs[a].sumk == SUMK_I128);
+        dec_err |= S.aggs[a].dec_check || (S.aggs[a].kind == DBG_AGG_AVG && S.aggs[a].sumk >= SUMK_I128);
     }
     // the table counters, in flight while the table is scanned (final: every inserting workgroup
     // has finished; write_group may still set decimal-overflow bits, reloaded below)
@@ -1901,7 +1903,7 @@ __device__ __forceinline__ bool finalize_small_body(const Spec& S, const BatchDe
         occ &= occ - 1;
         const u64 s = base + k;
         const u64* st = view + s * t.stride_words;
-        write_group(S, batches, t, s, st, st[0], p, sp, out);
+        write_group<W256>(S, batches, t, s, st, st[0], p, sp, out);
         p++;
     }
     mark(8);
@@ -2024,7 +2026,7 @@ __device__ __forceinline__ void fused_finalize(const Spec& S, const BatchDesc* b
     if (threadIdx.x == 0) atomicExch((unsigned long long*)(t.counters + CNT_FIN_TICKET), 0ULL);
     __syncthreads();
     if (kPhaseTrace && ff.trace && threadIdx.x == 0) ff.trace[5] = __builtin_amdgcn_s_memrealtime();
-    finalize_small_body<FUSED_FIN_SLOTS / FIN_NT>(S, batches, t, lds, ff.out, ff.totals, ff.host_mirror, ff.recycle, ff.seq,
+    finalize_small_body<FUSED_FIN_SLOTS / FIN_NT, false>(S, batches, t, lds, ff.out, ff.totals, ff.host_mirror, ff.recycle, ff.seq,
                                                   ff.trace);
     if (kPhaseTrace && ff.trace && threadIdx.x == 0) ff.trace[6] = __builtin_amdgcn_s_memrealtime();
 }
@@ -2035,7 +2037,7 @@ __device__ __forceinline__ void merge_parked(const Spec& S, const BatchDesc* bat
     if constexpr (CO) {  // c1: the parked count, loaded with the entry
         if (c1) at_add<AS>(asp<AS>(st + 1), c1);
     } else {
-        apply_state<AS, true, AS_GLB, false>(S, asp<AS>(st), r, batches);  // fast kernel: no String MIN/MAX (fast_eligible)
+        apply_state<AS, true, AS_GLB, false, false>(S, asp<AS>(st), r, batches);  // fast kernel: no String MIN/MAX, no Decimal256 (fast_eligible)
     }
 }
 
@@ -2300,7 +2302,7 @@ __device__ __forceinline__ void fused_chain(const Spec& S, const BatchDesc* batc
     // records); returns the parked entries (uniform)
     auto park = [&](u64* dst) -> u64 {
         if (lcount[0] > SCR_ENTRIES) {
-            flush_lds_direct<true, false, false>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
+            flush_lds_direct<true, false, false, false>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
             my_ovf += threadIdx.x == 0 ? 1u : 0u;
             return 0;
         }
@@ -2360,7 +2362,7 @@ __device__ __forceinline__ void fused_chain(const Spec& S, const BatchDesc* batc
         tickets[g] = 0;  // ready for the next launch on this table (all members have added)
         lcount[0] = lcount[1] = lcount[2] = 0;
     }
-    lds_table_init(S, lds, lds_slots, sw, nt);
+    lds_table_init<false>(S, lds, lds_slots, sw, nt);
     __syncthreads();
     for (u32 f = threadIdx.x; f < gsize * SCR_ENTRIES; f += nt) {
         const u64 b = (u64)g * SCR_GROUP + f / SCR_ENTRIES, k = f % SCR_ENTRIES;
@@ -2447,7 +2449,7 @@ __device__ __forceinline__ void fused_chain(const Spec& S, const BatchDesc* batc
     // overflow record, or a caller that keeps the table)
     // counters known without a load: an empty table at launch start, no overflow anywhere
     if constexpr (CO) finalize_count_only<T>(t, lds, ff, known, vcl);
-    else finalize_small_body<FUSED_FIN_SLOTS / FIN_NT>(S, batches, t, lds, ff.out, ff.totals, ff.host_mirror, ff.recycle, ff.seq,
+    else finalize_small_body<FUSED_FIN_SLOTS / FIN_NT, false>(S, batches, t, lds, ff.out, ff.totals, ff.host_mirror, ff.recycle, ff.seq,
                                                        ff.trace, true);
     if (kPhaseTrace && ff.trace && threadIdx.x == 0) ff.trace[6] = __builtin_amdgcn_s_memrealtime();
 }
@@ -2499,7 +2501,7 @@ __device__ __forceinline__ void fused_chain_tagged(const Spec& S, const BatchDes
     // possible overflow pushes ride on the ticket (uniform: lcount[0] is final).
     auto flush_if_large = [&]() -> bool {
         if (lcount[0] <= SCR_ENTRIES) return false;
-        flush_lds_direct<true, false, false>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
+        flush_lds_direct<true, false, false, false>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
         my_ovf += threadIdx.x == 0 ? 1u : 0u;
         return true;
     };
@@ -2595,7 +2597,7 @@ __device__ __forceinline__ void fused_chain_tagged(const Spec& S, const BatchDes
         lcount[1] = 0;
         if (flushed) lcount[0] = 0;
     }
-    if (flushed) lds_table_init(S, lds, lds_slots, sw, nt);
+    if (flushed) lds_table_init<false>(S, lds, lds_slots, sw, nt);
     __syncthreads();
     for (u32 f = threadIdx.x; f < gsize * SCR_ENTRIES; f += nt) {
         const u64 b = (u64)g * SCR_GROUP + f / SCR_ENTRIES;
@@ -2777,7 +2779,7 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
     v4u* vq = (v4u*)qkey;
     u64* vqb = qkey + 2 * WQ;
     if (kPhaseTrace && ff.trace && threadIdx.x == 0) atomicMin((unsigned long long*)ff.trace, (unsigned long long)__builtin_amdgcn_s_memrealtime());
-    lds_table_init(S, lds, lds_slots, sw, NT);
+    lds_table_init<false>(S, lds, lds_slots, sw, NT);
     if (threadIdx.x < 4) lcount[threadIdx.x] = 0;
     __syncthreads();
     u32 my_claims = 0;
@@ -2792,7 +2794,7 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
         if (ls >= 0) {
             wptr<AS_LDS> st = asp<AS_LDS>(lds + (u64)ls * sw);
             if (CO) at_add<AS_LDS>(st + 1, 1ULL);
-            else apply_row<AS_LDS, false>(S, st, B, i, batches, bid);
+            else apply_row<AS_LDS, false, false>(S, st, B, i, batches, bid);
             return;
         }
         bool claimed;
@@ -2805,7 +2807,7 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
         my_claims += claimed ? 1 : 0;
         wptr<AS_GLB> gst = asp<AS_GLB>(t.slots + gs * t.stride_words);
         if (CO) at_add<AS_GLB>(gst + 1, 1ULL);
-        else apply_row<AS_GLB, false>(S, gst, B, i, batches, bid);
+        else apply_row<AS_GLB, false, false>(S, gst, B, i, batches, bid);
     };
 
     u32 qn = 0;  // wave-uniform queue length
@@ -3114,7 +3116,7 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
         fused_chain<T, CO>(S, batches, B, lds, lds_slots, sw, lcount, NT, t, my_claims, my_ovf, ff);
         return;
     }
-    block_flush<true, false, false>(S, batches, B, lds, lds_slots, sw, lcount, NT, t, my_claims);
+    block_flush<true, false, false, false>(S, batches, B, lds, lds_slots, sw, lcount, NT, t, my_claims);
     if (kPhaseTrace && ff.trace && threadIdx.x == 0) atomicMax((unsigned long long*)ff.trace + 3, (unsigned long long)__builtin_amdgcn_s_memrealtime());
     if (ff.on) fused_finalize(S, batches, t, lds, ff);
 }
@@ -3190,6 +3192,10 @@ static bool fast_eligible(const Spec& S, const BatchDesc& hb, bool records) {
     // generic insert stages and flushes such states
     for (int a = 0; a < S.n_aggs; ++a)
         if ((S.aggs[a].kind == DBG_AGG_MIN || S.aggs[a].kind == DBG_AGG_MAX) && S.aggs[a].mmk == MMK_STR) return false;
+    // Decimal256 arguments likewise (apply_row<AS, false, false>, the fused finalize without the
+    // four-word results)
+    for (int a = 0; a < S.n_aggs; ++a)
+        if (S.aggs[a].arg_type == DBG_DECIMAL256) return false;
     const DCol& k = hb.keys[0];
     int ty = k.type;
     bool intlike = (ty >= DBG_INT8 && ty <= DBG_UINT64) || ty == DBG_DATE || ty == DBG_TIMESTAMP;

@@ -49,6 +49,7 @@ __host__ __device__ inline uint32_t type_width(int t) {
         case DBG_INT32: case DBG_UINT32: case DBG_FLOAT32: case DBG_DATE: return 4;
         case DBG_INT64: case DBG_UINT64: case DBG_FLOAT64: case DBG_TIMESTAMP: return 8;
         case DBG_DECIMAL128: return 16;
+        case DBG_DECIMAL256: return 32;
         default: return 0;
     }
 }
@@ -70,7 +71,7 @@ __device__ __forceinline__ bool dcol_valid(const DCol& c, u64 i) {
     return (gld<u8>(c.validity + (b >> 3)) >> (b & 7)) & 1;
 }
 
-// Raw value bits of a fixed-width cell, zero-extended to 64 bits (Decimal128: low word).
+// Raw value bits of a fixed-width cell, zero-extended to 64 bits (Decimal128 / Decimal256: word 0).
 __device__ __forceinline__ u64 dcol_bits(const DCol& c, u64 i) {
     if (c.type == DBG_BOOLEAN) {
         if (c.layout == LAYOUT_RECORD) return gld<u8>(c.data + i * c.stride) != 0;
@@ -87,6 +88,9 @@ __device__ __forceinline__ u64 dcol_bits(const DCol& c, u64 i) {
 }
 __device__ __forceinline__ u64 dcol_hi(const DCol& c, u64 i) {  // Decimal128 high word
     return gld<u64>(c.data + i * (u64)c.stride + 8);
+}
+__device__ __forceinline__ u64 dcol_word(const DCol& c, u64 i, int k) {  // Decimal256 word k (0 = least significant)
+    return gld<u64>(c.data + i * (u64)c.stride + 8 * k);
 }
 
 struct StrRef {
@@ -195,6 +199,26 @@ __device__ __forceinline__ u64 hash_i128(u64 lo, u64 hi) {
     return h;
 }
 
+// Decimal256: hash of i256::to_le_bytes (group_hash.rs:232-236) — hash_bytes over 32 bytes: four
+// full 8-byte blocks, no tail.
+__device__ __forceinline__ u64 hash_i256(u64 w0, u64 w1, u64 w2, u64 w3) {
+    const u64 M = 0xc6a4a7935bd1e995ULL, R = 47;
+    u64 h = 0xe17a1465ULL ^ (32ULL * M);
+    const u64 w[4] = {w0, w1, w2, w3};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        u64 k = w[i] * M;
+        k ^= k >> R;
+        k *= M;
+        h ^= k;
+        h *= M;
+    }
+    h ^= h >> R;
+    h *= M;
+    h ^= h >> R;
+    return h;
+}
+
 // Canonical bits of a float key: NaN -> f32::NAN / f64::NAN (group_hash.rs:238-258).
 __device__ __forceinline__ u64 canon_float_bits(int type, u64 b) {
     if (type == DBG_FLOAT32) {
@@ -214,6 +238,7 @@ __device__ __forceinline__ u64 hash_cell(const DCol& c, u64 i) {
             return hash_bytes(s.p, s.len);
         }
         case DBG_DECIMAL128: return hash_i128(dcol_bits(c, i), dcol_hi(c, i));
+        case DBG_DECIMAL256: return hash_i256(dcol_word(c, i, 0), dcol_word(c, i, 1), dcol_word(c, i, 2), dcol_word(c, i, 3));
         case DBG_BOOLEAN: return dcol_bits(c, i);
         case DBG_FLOAT32: case DBG_FLOAT64: return hash_prim(canon_float_bits(c.type, dcol_bits(c, i)));
         case DBG_INT8: case DBG_INT16: case DBG_INT32: case DBG_DATE:
@@ -253,6 +278,9 @@ __device__ __forceinline__ bool cell_equal(const DCol& a, u64 i, const DCol& b, 
             return x.len == y.len && bytes_equal(x.p, y.p, x.len);
         }
         case DBG_DECIMAL128: return dcol_bits(a, i) == dcol_bits(b, j) && dcol_hi(a, i) == dcol_hi(b, j);
+        case DBG_DECIMAL256:
+            return dcol_word(a, i, 0) == dcol_word(b, j, 0) && dcol_word(a, i, 1) == dcol_word(b, j, 1) &&
+                   dcol_word(a, i, 2) == dcol_word(b, j, 2) && dcol_word(a, i, 3) == dcol_word(b, j, 3);
         case DBG_FLOAT32: case DBG_FLOAT64:
             return canon_float_bits(a.type, dcol_bits(a, i)) == canon_float_bits(b.type, dcol_bits(b, j));
         default: return dcol_bits(a, i) == dcol_bits(b, j);
@@ -390,14 +418,18 @@ __device__ __forceinline__ bool eval_pred(const DNode* nodes, int n_nodes, const
 enum {
     SUMK_I64 = 0,  // wrapping 64-bit add (i8..i64 -> Int64, u8..u64 -> UInt64)
     SUMK_F64 = 1,  // f64 add
-    SUMK_I128 = 2  // 128-bit add with carry (Decimal128)
+    SUMK_I128 = 2,  // 128-bit add with carry (Decimal128)
+    SUMK_I256 = 3   // 256-bit add with carries (Decimal256, agg_dev.hpp add256)
 };
+// the AVG count word follows the sum words
+__host__ __device__ __forceinline__ int sum_words(int sumk) { return sumk == SUMK_I256 ? 4 : (sumk == SUMK_I128 ? 2 : 1); }
 enum {
     MMK_I64 = 0,  // signed (ints, date, timestamp, Decimal128 with precision <= 18)
     MMK_U64 = 1,  // unsigned
     MMK_F64 = 2,  // OrderedFloat order via the monotone u64 transform
     MMK_I128 = 3,  // Decimal128 with precision > 18: [seq, lo, hi] under a seqlock (agg.hpp at_minmax128)
-    MMK_STR = 4    // String: one word, (bid << 32) | row of the winning input row (agg_dev.hpp at_minmax_str)
+    MMK_STR = 4,   // String: one word, (bid << 32) | row of the winning input row (agg_dev.hpp at_minmax_str)
+    MMK_I256 = 5   // Decimal256: [seq, w0..w3] under the same seqlock (agg_dev.hpp at_minmax256)
 };
 #define STR_REF_NONE 0xFFFFFFFFFFFFFFFFULL  // MMK_STR identity: no value yet (a real reference has bits 48..63 clear)
 
@@ -434,6 +466,8 @@ __device__ __forceinline__ double f64_from_order_key(u64 k) {
     return __longlong_as_double((long long)b);
 }
 
+// W256 = false: for kernels compiled without the Decimal256 states (see apply_row)
+template <bool W256 = true>
 __host__ __device__ inline u64 state_init_word(const DAgg& a, int w) {
     if ((a.kind == DBG_AGG_MIN || a.kind == DBG_AGG_MAX) && a.mmk == MMK_STR) return STR_REF_NONE;
     if ((a.kind == DBG_AGG_MIN || a.kind == DBG_AGG_MAX) && a.mmk == MMK_I128) {
@@ -441,6 +475,13 @@ __host__ __device__ inline u64 state_init_word(const DAgg& a, int w) {
         if (w == 0) return 0ULL;
         const bool mn = a.kind == DBG_AGG_MIN;
         if (w == 1) return mn ? ~0ULL : 0ULL;
+        return mn ? 0x7fffffffffffffffULL : 0x8000000000000000ULL;
+    }
+    if (W256 && (a.kind == DBG_AGG_MIN || a.kind == DBG_AGG_MAX) && a.mmk == MMK_I256) {
+        // identity: i256::MAX for MIN, i256::MIN for MAX; word 0 is the sequence counter
+        if (w == 0) return 0ULL;
+        const bool mn = a.kind == DBG_AGG_MIN;
+        if (w < 4) return mn ? ~0ULL : 0ULL;
         return mn ? 0x7fffffffffffffffULL : 0x8000000000000000ULL;
     }
     if (a.kind == DBG_AGG_MIN) {

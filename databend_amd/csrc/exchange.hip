@@ -182,7 +182,7 @@ static void payload_owned(u32 d, u32 n, u32& lo, u32& hi) {
 }
 
 static int payload_check(dbg_agg_handle* h) {
-    REFUSE_STR_MINMAX(h, "payload exchange");
+    REFUSE_HANDLE_LOCAL(h, "payload exchange");
     if (!h->pp) return fail(DBG_ERR_UNSUPPORTED, "payload exchange: the handle is not in partitioned mode (dbg_agg_set_strategy)");
     if (h->spec.pp_str) return fail(DBG_ERR_UNSUPPORTED, "payload exchange: string keys (records may reference local rows)");
     return DBG_OK;
@@ -393,7 +393,7 @@ int dbg_payload_exchange_plan(const dbg_agg_params* params, uint32_t n_ranks, ui
     Spec S;
     std::vector<dbg_datatype> rt;
     RETURN_IF(build_spec(params, S, rt));
-    if (has_str_minmax(S)) return fail(DBG_ERR_UNSUPPORTED, "dbg_payload_exchange_plan: String min/max states are row references local to a handle");
+    if (const char* why = handle_local_reason(S)) return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_payload_exchange_plan: ") + why);
     const uint32_t w[2] = {S.pp_rw_raw, S.pp_rw_state};
     if (widths) {
         widths[0] = w[0];
@@ -437,7 +437,7 @@ static int all_ok(dbg_comm* c, RcclApi& R, hipStream_t s, bool ok, int* bad_rank
 
 int dbg_agg_exchange_payload(dbg_comm* c, dbg_agg_handle* h, dbg_exchange_stats* stats) {
     if (!c || !h) return fail(DBG_ERR_INVALID, "null argument");
-    REFUSE_STR_MINMAX(h, "payload exchange");
+    REFUSE_HANDLE_LOCAL(h, "payload exchange");
     if (h->device != c->device) return fail(DBG_ERR_INVALID, "communicator and table are on different devices");
     RcclApi& R = rccl_api();
     if (!R.ok) return fail(DBG_ERR_UNSUPPORTED, R.err);
@@ -532,7 +532,7 @@ int dbg_agg_exchange_payload(dbg_comm* c, dbg_agg_handle* h, dbg_exchange_stats*
 // the payload (one level-1 segment per chunk and source), like dbg_agg_exchange_payload.
 int dbg_agg_exchange_payload_chunk(dbg_comm* c, dbg_agg_handle* h, int last, dbg_exchange_stats* stats) {
     if (!c || !h) return fail(DBG_ERR_INVALID, "null argument");
-    REFUSE_STR_MINMAX(h, "payload exchange");
+    REFUSE_HANDLE_LOCAL(h, "payload exchange");
     if (h->device != c->device) return fail(DBG_ERR_INVALID, "communicator and table are on different devices");
     RcclApi& R = rccl_api();
     if (!R.ok) return fail(DBG_ERR_UNSUPPORTED, R.err);
@@ -676,7 +676,7 @@ int dbg_merge_exchange_plan(const dbg_agg_params* params, uint32_t n_ranks, uint
     Spec S;
     std::vector<dbg_datatype> rt;
     RETURN_IF(build_spec(params, S, rt));
-    if (has_str_minmax(S)) return fail(DBG_ERR_UNSUPPORTED, "dbg_merge_exchange_plan: String min/max states are row references local to a handle");
+    if (const char* why = handle_local_reason(S)) return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_merge_exchange_plan: ") + why);
     if (record_width) *record_width = S.rec_width;
     merge_plan(n_ranks, rank, S.rec_width, all_sizes, send_bytes, recv_bytes, recv_records);
     return DBG_OK;
@@ -708,8 +708,8 @@ static int xrecv_buffer(dbg_agg_handle* fh, int k, u64 bytes, void** out) {
 
 int dbg_agg_exchange(dbg_comm* c, dbg_agg_handle* partial, dbg_agg_handle* final_h, dbg_exchange_stats* stats) {
     if (!c || !partial || !final_h) return fail(DBG_ERR_INVALID, "null argument");
-    REFUSE_STR_MINMAX(partial, "dbg_agg_exchange");
-    REFUSE_STR_MINMAX(final_h, "dbg_agg_exchange");
+    REFUSE_HANDLE_LOCAL(partial, "dbg_agg_exchange");
+    REFUSE_HANDLE_LOCAL(final_h, "dbg_agg_exchange");
     if (partial->device != c->device || final_h->device != c->device)
         return fail(DBG_ERR_INVALID, "communicator and tables are on different devices");
     if (partial->spec.n_keys != final_h->spec.n_keys || partial->spec.n_aggs != final_h->spec.n_aggs ||

@@ -25,6 +25,7 @@ inline int type_width(int t) {
         case DBG_INT32: case DBG_UINT32: case DBG_FLOAT32: case DBG_DATE: return 4;
         case DBG_INT64: case DBG_UINT64: case DBG_FLOAT64: case DBG_TIMESTAMP: return 8;
         case DBG_DECIMAL128: return 16;
+        case DBG_DECIMAL256: return 32;
         default: return 0;
     }
 }

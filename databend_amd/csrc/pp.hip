@@ -1290,7 +1290,7 @@ __device__ __forceinline__ void pp_write_fixed_row(const Spec& S, const l64* e, 
         if (out.key_valid[c]) out.key_valid[c][row] = v ? 1 : 0;
     }
     const u64* st = (const u64*)(e + kw8);
-    for (int a = 0; a < S.n_aggs; ++a) write_agg(S, a, st, row, out, err);
+    for (int a = 0; a < S.n_aggs; ++a) write_agg<false>(S, a, st, row, out, err);  // no Decimal256 here (Spec::pp_ok)
 }
 
 template <typename R>
@@ -1388,7 +1388,7 @@ __global__ void __launch_bounds__(PP_AGG_NT) pp_agg_kernel(const Spec* __restric
                 const u64 pm = pp_mix(pp_hash_of(S, rk));
                 const int ls = pp_find(S, batches, slots, cap, sw, rk, pm, list, &nlist);
                 if (ls >= 0)
-                    apply_state<AS_LDS, false, AS_GLB>(S, (wptr<AS_LDS>)(slots + (size_t)ls * sw + kw8),
+                    apply_state<AS_LDS, false, AS_GLB, true, false>(S, (wptr<AS_LDS>)(slots + (size_t)ls * sw + kw8),
                                                        (const u64*)(rk.p + S.pp_kw) - 1, batches);
                 else
                     pp_store_rec(sout + (s0 + atomicAdd(&novf[1], 1u)) * rws, rk, rws);
@@ -1614,7 +1614,7 @@ __global__ void __launch_bounds__(PP_AGG_NT) pp_agg_rc_kernel(const Spec* __rest
                                 write_bytes(out.cols.key_data[c], row, wd, lo, hi);
                                 if (out.cols.key_valid[c]) out.cols.key_valid[c][row] = v ? 1 : 0;
                             }
-                            for (int a = 0; a < S.n_aggs; ++a) write_agg(S, a, st, row, out.cols, out.tot + PPT_ERR);
+                            for (int a = 0; a < S.n_aggs; ++a) write_agg<false>(S, a, st, row, out.cols, out.tot + PPT_ERR);
                         }
                     } else if (row < out.grec_cap) {
                         u64* d = (u64*)(out.grec + row * S.pp_rw_state);
@@ -2938,7 +2938,7 @@ __global__ void __launch_bounds__(PP_GNT) pp_grec_write_kernel(const Spec* __res
         }
         if (in && r < out.cap_groups) {
             const u64* st = (const u64*)(k + S.pp_kw) - 1;
-            for (int a = 0; a < S.n_aggs; ++a) write_agg(S, a, st, r, out, err);
+            for (int a = 0; a < S.n_aggs; ++a) write_agg<false>(S, a, st, r, out, err);
         }
     }
 }

@@ -1029,6 +1029,8 @@ bool target_ok(int ptype, int tlen, const dbg_datatype& t, u32& width) {
         case DBG_PQ_FLOAT: return t.type == DBG_FLOAT32;
         case DBG_PQ_DOUBLE: return t.type == DBG_FLOAT64;
         case DBG_PQ_BYTE_ARRAY: return t.type == DBG_STRING;
+        // Decimal256 targets (FIXED_LEN_BYTE_ARRAY of 17..32 bytes) are not decoded here: false for every
+        // physical type, so the caller gets DBG_ERR_UNSUPPORTED
         case DBG_PQ_FIXED_LEN_BYTE_ARRAY: return t.type == DBG_DECIMAL128 && tlen >= 1 && tlen <= 16;
         default: return false;
     }
@@ -1840,7 +1842,7 @@ bool nat_int_target(int t, u32& w) {
         case DBG_INT16: case DBG_UINT16: w = 2; return true;
         case DBG_INT32: case DBG_UINT32: case DBG_DATE: w = 4; return true;
         case DBG_INT64: case DBG_UINT64: case DBG_TIMESTAMP: w = 8; return true;
-        default: return false;
+        default: return false;  // Decimal256 (i256 pages) included: decoded on the CPU
     }
 }
 

@@ -65,8 +65,10 @@ class DeviceColumn:
         offs = self.offsets.cpu().numpy().view(np.uint64) if self.offsets is not None else None
         if t == abi.BOOLEAN:
             data = np.unpackbits(raw, bitorder="little")[:n].astype(bool)
-        elif t in (abi.STRING, abi.DECIMAL128):
+        elif t == abi.STRING:
             data = raw
+        elif t in (abi.DECIMAL128, abi.DECIMAL256):
+            data = raw[:n * self.dtype.width]
         else:
             data = raw.view(self.dtype.np_dtype)[:n]
         val = None

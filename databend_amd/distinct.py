@@ -107,6 +107,10 @@ def _check_supported(keys: Sequence[DataType], functions: Sequence[AggregateFunc
             raise Unsupported(abi.DBG_ERR_UNSUPPORTED, f"{f.display_name}: DISTINCT needs an argument")
         if f.distinct and f.arg.type_id == abi.BOOLEAN:
             raise Unsupported(abi.DBG_ERR_UNSUPPORTED, "DISTINCT over Boolean stays on the CPU path")
+    # pair tables and the plain aggregates' states travel as records (at most 16 bytes per key or
+    # state value): no Decimal256 keys or arguments
+    if any(t.type_id == abi.DECIMAL256 for t in keys) or any(f.arg is not None and f.arg.type_id == abi.DECIMAL256 for f in functions):
+        raise Unsupported(abi.DBG_ERR_UNSUPPORTED, "Decimal256 with DISTINCT stays on the CPU path")
     if any(t.type_id == abi.BOOLEAN for t in keys):
         raise Unsupported(abi.DBG_ERR_UNSUPPORTED, "Boolean group keys with DISTINCT stay on the CPU path")
     for f in functions:

@@ -140,6 +140,9 @@ class FilterProgram:
             n.i128_lo = u & ((1 << 64) - 1)
             hi = u >> 64
             n.i128_hi = hi - (1 << 64) if hi >= (1 << 63) else hi
+        elif t == abi.DECIMAL256:  # the node carries a 128-bit constant; the library refuses such columns too
+            from .ffi import Unsupported
+            raise Unsupported(abi.DBG_ERR_UNSUPPORTED, "filter: predicates over a Decimal256 column stay on the CPU path")
         elif t in (abi.UINT8, abi.UINT16, abi.UINT32, abi.UINT64):
             u = int(v) & ((1 << 64) - 1)
             n.i64 = u - (1 << 64) if u >= (1 << 63) else u

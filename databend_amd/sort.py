@@ -91,7 +91,8 @@ def sort(columns: Sequence[DeviceColumn], descriptions: Sequence[SortColumnDescr
     if not descriptions:
         raise ValueError("sort: no sort description")
     d = descriptions[0]
-    one_number = len(descriptions) == 1 and columns[d.offset].dtype.type_id not in (abi.STRING, abi.DECIMAL128)
+    # Decimal256 sort keys are refused by both entry points (DBG_ERR_UNSUPPORTED)
+    one_number = len(descriptions) == 1 and columns[d.offset].dtype.type_id not in (abi.STRING, abi.DECIMAL128, abi.DECIMAL256)
     if one_number:
         idx = sort_limit_indices(columns[d.offset], d.asc, d.nulls_first, limit)
     else:

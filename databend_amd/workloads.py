@@ -367,7 +367,7 @@ def _dev_to_host(c: DeviceColumn, n: int) -> Column:
     else:
         offs = None
         data = c.data[: n * t.width].cpu().numpy().copy()
-        if t.type_id not in (abi.DECIMAL128,):
+        if t.type_id not in (abi.DECIMAL128, abi.DECIMAL256):
             data = data.view(t.np_dtype)
     val = None
     if t.nullable and c.validity is not None:

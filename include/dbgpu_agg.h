@@ -47,7 +47,7 @@ enum {
     DBG_ERR_DEVICE = 6       /* HIP runtime failure */
 };
 
-/* ---- data types (EXP/types/: Number, Decimal128, Date, Timestamp, String, Boolean) ---- */
+/* ---- data types (EXP/types/: Number, Decimal128 / Decimal256, Date, Timestamp, String, Boolean) ---- */
 typedef enum {
     DBG_INT8 = 0,
     DBG_INT16 = 1,
@@ -63,13 +63,17 @@ typedef enum {
     DBG_DATE = 11,       /* i32 days since epoch */
     DBG_TIMESTAMP = 12,  /* i64 microseconds since epoch */
     DBG_STRING = 13,     /* bytes + offsets */
-    DBG_BOOLEAN = 14     /* bitmap */
+    DBG_BOOLEAN = 14,    /* bitmap */
+    /* i256 LE (ethnum::i256: four u64 words, word 0 least significant), 32 bytes per value, data
+     * 8-byte aligned; precision 39..76, scale <= precision (DecimalDataType::from_size,
+     * EXP/types/decimal.rs:903-921), anything else is DBG_ERR_INVALID.  See "Decimal256" below. */
+    DBG_DECIMAL256 = 15
 } dbg_type;
 
 typedef struct dbg_datatype {
     int32_t type;      /* dbg_type */
-    uint8_t precision; /* Decimal128 only */
-    uint8_t scale;     /* Decimal128 only */
+    uint8_t precision; /* Decimal128 / Decimal256 only */
+    uint8_t scale;     /* Decimal128 / Decimal256 only */
     uint8_t nullable;  /* DataType::Nullable(..) wrapper */
     uint8_t reserved;
 } dbg_datatype;
@@ -224,6 +228,31 @@ int dbg_agg_result(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_column* 
  * the aggregates' string sizes).  dbg_agg_compact is a no-op (*compacted = 0).  The serialized
  * form (borsh Option<String>) is not built yet. */
 int dbg_agg_result_string_bytes(dbg_agg_handle* h, uint64_t* agg_string_bytes /* n_aggs */);
+/* Decimal256 (DBG_DECIMAL256) arguments and group keys.
+ * Result types (dbg_agg_result_type), after the reference's factories: COUNT UInt64; SUM
+ * Decimal256(76, s) (FUN/aggregate_sum.rs:224-250); AVG Decimal256(76, max(s, 4))
+ * (FUN/aggregate_avg.rs:261-270); MIN / MAX the argument's own type; DBG_AGG_AVG_SQL is
+ * DBG_ERR_UNSUPPORTED (the 256-bit rounding divide is not built).  Results are 32 bytes per group;
+ * a NULL group holds zeros.
+ *  - SUM (DecimalSumState<false, Decimal256Type>: every Decimal256 has precision > 18, so no range
+ *    check) wraps modulo 2^256 as a release build of the reference does; it never fails.
+ *  - AVG (DecimalAvgState<true, Decimal256Type>, FUN/aggregate_avg.rs:141-153, 173-199): the sum
+ *    must lie within +-(10^76 - 1), sum * 10^scale_add (scale_add 0..4) must fit an i256, and the
+ *    quotient by the count truncates toward zero; a failed check makes the call that computes the
+ *    results (dbg_agg_result, dbg_agg_finalize_into / _wait) return DBG_ERR_OVERFLOW, as for
+ *    Decimal128.  The reference checks the range after every add, so whether it raises can
+ *    depend on the order of the rows; this library checks each group's final sum only (inputs
+ *    whose running sums stay within range in every order give the same answer in both).
+ *  - MIN / MAX compare as signed 256-bit integers.
+ *  - A Decimal256 group key is hashed as `to_le_bytes().agg_hash()` (EAGG/group_hash.rs:232-236).
+ * Records, the partitioned payload, the exchanges and the serialized states carry keys and states
+ * of at most 16 bytes, so a handle whose spec has a Decimal256 key or argument is handle-local
+ * exactly as one with a String MIN/MAX is: it runs the HBM table only and returns
+ * DBG_ERR_UNSUPPORTED (naming Decimal256) from the entry points listed above, except that
+ * dbg_agg_finalize_into(_async) works; dbg_agg_compact is a no-op (*compacted = 0).  Filter
+ * predicates over a Decimal256 column, dbg_take_fixed, dbg_sort_limit_* keys, the legacy hash
+ * methods, DISTINCT and scan targets of this type are DBG_ERR_UNSUPPORTED for now; a filter over
+ * other columns fused with Decimal256 keys or arguments works. */
 /* AggregateMeta::Serialized (AGG/aggregate_meta.rs:44-109; EAGG/payload_flush.rs:129-164): the
  * partial states as Binary columns, one per aggregate, + the group columns — what the reference
  * ships over Flight or spills, so a CPU final stage (or a GPU one) merges them.  Each row is the
