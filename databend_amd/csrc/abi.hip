@@ -113,20 +113,19 @@ void* prof_scope_begin(const char* name, hipStream_t s) { return prof::enabled ?
 void prof_scope_end(void* p) { delete (prof::Scope*)p; }
 
 
-int dev_alloc(void** p, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess) return fail(DBG_ERR_OOM, std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
+// `bytes` of device memory the handle keeps until its next reset: h->owned.back()
+static int own_alloc(dbg_agg_handle* h, size_t bytes) {
+    DevBuf b;
+    RETURN_IF(b.ensure(bytes));
+    h->owned.push_back(std::move(b));
     return DBG_OK;
 }
 
 static int own_copy(dbg_agg_handle* h, const void* src, size_t bytes, const void** out) {
-    DevBuf b;
-    b.bytes = bytes;
-    RETURN_IF(dev_alloc(&b.p, bytes));
-    h->owned.push_back(b);
-    if (bytes) HIPCHECK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    *out = b.p;
+    RETURN_IF(own_alloc(h, bytes));
+    u8* const p = h->owned.back();
+    if (bytes) HIPCHECK(hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, h->stream));
+    *out = p;
     return DBG_OK;
 }
 
@@ -362,9 +361,9 @@ static TableDesc table_desc(dbg_agg_handle* h) {
     t.probe_limit = (u32)std::min<u64>(h->cap, 512);
     t.counters = h->counters;
     t.ovf_rows = h->ovf_rows;
-    t.ovf_rows_cap = h->ovf_rows_cap;
+    t.ovf_rows_cap = h->ovf_rows.cap();
     t.ovf_recs = h->ovf_recs;
-    t.ovf_recs_cap = h->ovf_recs_cap;
+    t.ovf_recs_cap = h->ovf_recs.cap() / (u64)h->spec.tstride;
     t.scratch = h->scratch;
     t.scr_blocks = h->scr_blocks;
 
@@ -389,28 +388,25 @@ static u64 pow2_at_least(u64 x) {
     return p;
 }
 
-static int alloc_table(dbg_agg_handle* h, u64 cap, u64** out) {
-    size_t bytes = (size_t)(cap + 1) * h->spec.tstride * 8;
-    RETURN_IF(dev_alloc((void**)out, bytes));
+static int alloc_table(dbg_agg_handle* h, u64 cap, Buf<u64>& out) {
+    RETURN_IF(out.ensure((cap + 1) * (u64)h->spec.tstride));
     prof::Scope ps("table_init", h->stream);
-    launch_table_init(h->stream, h->dspec, h->spec, *out, cap);
+    launch_table_init(h->stream, h->dspec, h->spec, out, cap);
     return DBG_OK;
 }
 
 static int grow_table(dbg_agg_handle* h, u64 new_cap) {
     table_init_now(h);  // the old table is rehashed below
-    u64* ns = nullptr;
-    RETURN_IF(alloc_table(h, new_cap, &ns));
-    u64* old = h->slots;
+    Buf<u64> old;
+    RETURN_IF(alloc_table(h, new_cap, old));
+    std::swap(old, h->slots);
     u64 old_cap = h->cap;
-    h->slots = ns;
     h->cap = new_cap;
     {
         prof::Scope ps("agg_rehash", h->stream);
         launch_rehash(h->stream, h->dspec, h->spec, h->dbatches, old, old_cap, table_desc(h));
     }
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    HIPCHECK(hipFree(old));
+    HIPCHECK(hipStreamSynchronize(h->stream));  // the old table is freed behind it
     return DBG_OK;
 }
 
@@ -462,7 +458,8 @@ static int resolve_overflow(dbg_agg_handle* h) {
 // Make sure the deferred-overflow lists can hold everything the next launch may push.
 static int ensure_ovf(dbg_agg_handle* h, u64 add_rows, u64 add_recs) {
     u64 need_rows = h->pending_rows + add_rows, need_recs = h->pending_recs + add_recs;
-    if (need_rows <= h->ovf_rows_cap && need_recs <= h->ovf_recs_cap) {
+    const u64 rec_words = (u64)h->spec.tstride;
+    if (need_rows <= h->ovf_rows.cap() && need_recs * rec_words <= h->ovf_recs.cap()) {
         h->pending_rows = need_rows;
         h->pending_recs = need_recs;
         return DBG_OK;
@@ -471,16 +468,8 @@ static int ensure_ovf(dbg_agg_handle* h, u64 add_rows, u64 add_recs) {
     RETURN_IF(resolve_overflow(h));
     need_rows = add_rows;
     need_recs = add_recs;
-    if (need_rows > h->ovf_rows_cap) {
-        if (h->ovf_rows) HIPCHECK(hipFree(h->ovf_rows));
-        h->ovf_rows_cap = std::max<u64>(need_rows, 1024);
-        RETURN_IF(dev_alloc((void**)&h->ovf_rows, h->ovf_rows_cap * 8));
-    }
-    if (need_recs > h->ovf_recs_cap) {
-        if (h->ovf_recs) HIPCHECK(hipFree(h->ovf_recs));
-        h->ovf_recs_cap = std::max<u64>(need_recs, 1024);
-        RETURN_IF(dev_alloc((void**)&h->ovf_recs, h->ovf_recs_cap * h->spec.tstride * 8));
-    }
+    if (need_rows > h->ovf_rows.cap()) RETURN_IF(h->ovf_rows.ensure(need_rows, 1024));
+    if (need_recs * rec_words > h->ovf_recs.cap()) RETURN_IF(h->ovf_recs.ensure(need_recs * rec_words, 1024 * rec_words));
     h->pending_rows = need_rows;
     h->pending_recs = need_recs;
     return DBG_OK;
@@ -492,25 +481,15 @@ static int ensure_ovf(dbg_agg_handle* h, u64 add_rows, u64 add_recs) {
 static int new_batch(dbg_agg_handle* h, BatchDesc** staging, u32* bid) {
     if (h->n_batches >= 0xFFFE) return fail(DBG_ERR_UNSUPPORTED, "more than 65534 batches before reset");
     u32 id = h->n_batches + 1;
-    if (id >= h->batch_cap) {
-        u64 ncap = std::max<u64>(64, h->batch_cap * 2);
-        BatchDesc* nb = nullptr;
-        RETURN_IF(dev_alloc((void**)&nb, ncap * sizeof(BatchDesc)));
-        if (h->dbatches) {
-            HIPCHECK(hipMemcpyAsync(nb, h->dbatches, h->batch_cap * sizeof(BatchDesc), hipMemcpyDeviceToDevice, h->stream));
-            HIPCHECK(hipStreamSynchronize(h->stream));
-            HIPCHECK(hipFree(h->dbatches));
-        }
-        h->dbatches = nb;
-        h->batch_cap = ncap;
-    }
+    if (id >= h->dbatches.cap())
+        RETURN_IF(h->dbatches.grow_keep(std::max<u64>(64, h->dbatches.cap() * 2), h->dbatches.cap(), h->stream));
     // pinned staging descriptors are pooled: slot id is reused after dbg_agg_reset (which
     // synchronises the stream, so the previous upload from it has completed)
     while (h->pinned_descs.size() <= id) {
-        BatchDesc* chunk = nullptr;
-        HIPCHECK(hipHostMalloc((void**)&chunk, 64 * sizeof(BatchDesc), hipHostMallocDefault));
-        h->pinned_chunks.push_back(chunk);
+        PinnedBuf<BatchDesc> chunk;
+        RETURN_IF(chunk.ensure(64));
         for (int k = 0; k < 64; ++k) h->pinned_descs.push_back(chunk + k);
+        h->pinned_chunks.push_back(std::move(chunk));
     }
     BatchDesc* st = h->pinned_descs[id];
     memset(st, 0, sizeof(BatchDesc));
@@ -701,7 +680,7 @@ int dbg_agg_create(const dbg_agg_params* params, dbg_agg_handle** out) {
     if (hipSetDevice(h->device) != hipSuccess) return cleanup(fail(DBG_ERR_DEVICE, "hipSetDevice failed"));
     if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return cleanup(fail(DBG_ERR_DEVICE, "hipStreamCreate failed"));
     h->stream = h->own_stream;
-    if ((rc = dev_alloc((void**)&h->counters, CNT_WORDS * 8)) != DBG_OK) return cleanup(rc);
+    if ((rc = h->counters.ensure(CNT_WORDS)) != DBG_OK) return cleanup(rc);
     if (hipMemset(h->counters, 0, CNT_WORDS * 8) != hipSuccess) return cleanup(fail(DBG_ERR_DEVICE, "memset"));
     h->spec.err = h->counters + CNT_ERR;  // error bits raised from inside state updates
     {
@@ -710,10 +689,10 @@ int dbg_agg_create(const dbg_agg_params* params, dbg_agg_handle** out) {
         h->spec.x_pp_cap = cx ? std::max<u32>(64, (u32)atoi(cx) & ~3u) : ~0u;
         h->spec.x_pp_desc = (fd && fd[0] == '1') ? 1 : 0;
     }
-    if ((rc = dev_alloc((void**)&h->dspec, sizeof(Spec))) != DBG_OK) return cleanup(rc);
+    if ((rc = h->dspec.ensure(1)) != DBG_OK) return cleanup(rc);
     if (hipMemcpy(h->dspec, &h->spec, sizeof(Spec), hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail(DBG_ERR_DEVICE, "spec upload"));
-    if (hipHostMalloc((void**)&h->hcounters, (CNT_WORDS + DBG_MAX_KEYS + 8) * 8, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return cleanup(fail(DBG_ERR_OOM, "pinned"));
-    if (hipHostGetDevicePointer((void**)&h->hcounters_dev, h->hcounters, 0) != hipSuccess) h->hcounters_dev = nullptr;
+    if ((rc = h->hcounters.ensure(CNT_WORDS + DBG_MAX_KEYS + 8)) != DBG_OK) return cleanup(rc);
+    if (hipHostGetDevicePointer((void**)&h->hcounters_dev, h->hcounters.get(), 0) != hipSuccess) h->hcounters_dev = nullptr;
     // initial capacity: 2x the hint, or 1024 slots (the CPU table starts at 32768 =
     // AggregateHashTable::initial_capacity(); on the GPU growth is a cheap rehash kernel and a
     // small table keeps init / finalize scans short for low-cardinality queries: 4096 -> 1024
@@ -722,10 +701,10 @@ int dbg_agg_create(const dbg_agg_params* params, dbg_agg_handle** out) {
     u64 hint = params->capacity_hint ? params->capacity_hint : 512;
     h->cap = pow2_at_least(std::max<u64>(hint * 2, 1024));
     h->init_cap = h->cap;
-    if ((rc = alloc_table(h, h->cap, &h->slots)) != DBG_OK) return cleanup(rc);
+    if ((rc = alloc_table(h, h->cap, h->slots)) != DBG_OK) return cleanup(rc);
     // parking rows for every workgroup of an insert launch (launch_insert caps its grid here)
     h->scr_blocks = DBG_INSERT_MAX_BLOCKS;
-    if ((rc = dev_alloc((void**)&h->scratch, scr_words(h->scr_blocks, (u32)h->spec.stride_words) * 8)) != DBG_OK) return cleanup(rc);
+    if ((rc = h->scratch.ensure(scr_words(h->scr_blocks, (u32)h->spec.stride_words))) != DBG_OK) return cleanup(rc);
     if (hipMemset(h->scratch, 0, (size_t)h->scr_blocks * 16) != hipSuccess) return cleanup(fail(DBG_ERR_DEVICE, "memset"));
 
     // the (empty) batch table
@@ -742,31 +721,9 @@ void dbg_agg_destroy(dbg_agg_handle* h) {
     if (!h) return;
     hipSetDevice(h->device);
     if (h->stream) hipStreamSynchronize(h->stream);
-    for (auto& b : h->owned) hipFree(b.p);
-    for (auto& b : h->xrecv)
-        if (b.p) hipFree(b.p);
-    for (auto* p : h->pinned_chunks) hipHostFree(p);
-    void* bufs[] = {h->scratch, h->slots, h->counters, h->ovf_rows, h->ovf_recs, h->dbatches, h->dspec, h->d_pos, h->d_str_pos,
-                    h->d_part_pos, h->d_part_str_pos, h->d_part_str_base, h->d_lpart, h->vbytes, h->part_sorted, h->part_bounds,
-                    h->part_temp, h->ser_err, h->dense, h->part_status};
-    for (void* p : bufs)
-        if (p) hipFree(p);
-    for (auto& K : h->ppk) {
-        void* kb[] = {K.l1, K.a, K.b, K.part, K.dig};
-        for (void* q : kb)
-            if (q) hipFree(q);
-    }
-    void* pb[] = {h->pp_cnt, h->pp_off, h->pp_scan_tmp, h->pp_mid, h->pp_dchunks, h->pp_dc0, h->pp_tot, h->pp_set, h->pp_grec, h->pp_blk,
-                  h->pp_spill};
-    for (void* q : pb)
-        if (q) hipFree(q);
-    void* ph[] = {h->pp_hchunks, h->pp_hc0, h->pp_hpart, h->pp_htot};
-    for (void* q : ph)
-        if (q) hipHostFree(q);
-    if (h->hcounters) hipHostFree(h->hcounters);
     if (h->switch_ev) hipEventDestroy(h->switch_ev);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
-    delete h;
+    delete h;  // frees every buffer: on the handle's device, behind the synchronisation above
 }
 
 int dbg_agg_set_stream(dbg_agg_handle* h, void* s) {
@@ -795,7 +752,6 @@ int dbg_agg_reset(dbg_agg_handle* h) {
     // be read by queued work: wait if any were queued since the last synchronisation
     if (!h->owned.empty() || h->uploads_pending) {
         HIPCHECK(hipStreamSynchronize(h->stream));
-        for (auto& b : h->owned) HIPCHECK(hipFree(b.p));
         h->owned.clear();
         h->uploads_pending = false;
     }
@@ -823,29 +779,21 @@ int dbg_agg_reset(dbg_agg_handle* h) {
     return DBG_OK;
 }
 
-static int ensure_buf(u64** p, u64* cap, u64 n);
-
 // Radix-partitioned COUNT(*) insert of a high-cardinality batch (part.hip); buffers grow only.
 static int part_insert(dbg_agg_handle* h, const BatchDesc* st, u32 bid, u64 rows, u32 sb, bool on_device_insert, bool was_clean) {
     (void)bid;
     const int width = (int)st->keys[0].width;
     size_t tb = part_temp_bytes(width, rows, sb, h->cap);
     if (!tb) return fail(DBG_ERR_INTERNAL, "rocprim radix_sort_keys sizing failed");
-    if (tb > h->part_temp_cap) {
-        if (h->part_temp) HIPCHECK(hipFree(h->part_temp));
-        h->part_temp = nullptr;
-        h->part_temp_cap = 0;
-        RETURN_IF(dev_alloc(&h->part_temp, tb));
-        h->part_temp_cap = tb;
-    }
-    RETURN_IF(ensure_buf(&h->part_sorted, &h->part_sorted_cap, rows));
-    RETURN_IF(ensure_buf(&h->part_bounds, &h->part_bounds_cap, (h->cap >> sb) + 1));
+    if (tb > h->part_temp.cap()) RETURN_IF(h->part_temp.ensure(tb));
+    RETURN_IF(h->part_sorted.ensure(rows, 1024));
+    RETURN_IF(h->part_bounds.ensure((h->cap >> sb) + 1, 1024));
     prof::Scope ps("agg_insert", h->stream);
     const char* step = "";
     // an empty table whose initialisation is still deferred: the slice kernel writes every slot
     const bool empty = h->init_pending;
     h->init_pending = false;
-    hipError_t e = launch_part_sort(h->stream, *st, rows, h->cap, sb, h->part_temp, h->part_temp_cap, h->part_sorted, h->part_bounds,
+    hipError_t e = launch_part_sort(h->stream, *st, rows, h->cap, sb, h->part_temp, h->part_temp.cap(), h->part_sorted, h->part_bounds,
                                     &step);
     // EXPERIMENT (EXP=1 build): DBG_X_PART_DIRECT=0 keeps the table stage in the insert
     static const bool direct_on = !(X_ENV("DBG_X_PART_DIRECT") && X_ENV("DBG_X_PART_DIRECT")[0] == '0');
@@ -877,35 +825,6 @@ static int part_flush(dbg_agg_handle* h) {
 // ------------------------------------------------------------------------------------------
 // partitioned payload (pp.hip), host side
 // ------------------------------------------------------------------------------------------
-}  // extern "C" (templates need C++ linkage)
-template <typename T>
-static int ensure_dev(T** p, u64* cap, u64 n) {
-    if (n <= *cap && *p) return DBG_OK;
-    if (*p) HIPCHECK(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const u64 c = std::max<u64>(n, 64);
-    RETURN_IF(dev_alloc((void**)p, c * sizeof(T)));
-    *cap = c;
-    return DBG_OK;
-}
-template <typename T>
-static int ensure_pinned(dbg_agg_handle* h, T** p, u64* cap, u64 n) {
-    if (n <= *cap && *p) return DBG_OK;
-    if (*p) {
-        HIPCHECK(hipStreamSynchronize(h->stream));  // a queued copy may still read it
-        HIPCHECK(hipHostFree(*p));
-    }
-    *p = nullptr;
-    *cap = 0;
-    const u64 c = std::max<u64>(n, 1024);
-    HIPCHECK(hipHostMalloc((void**)p, c * sizeof(T), hipHostMallocDefault));
-    *cap = c;
-    return DBG_OK;
-}
-
-extern "C" {
-
 #define PP_MIN_ROWS (1ULL << 22)
 #define PP_MIN_GROUPS (1ULL << 20)
 #define PP_SET_CAP (1ULL << 19)  // 2^18 samples at most: <= 50 % load
@@ -938,7 +857,7 @@ static int pp_maybe_switch(dbg_agg_handle* h, u32 bid, u64 rows) {
         if (ratio * (double)rows > (double)PP_MIN_GROUPS && ratio > 0.5) h->pp = true;
         return DBG_OK;
     }
-    if (!h->pp_set) RETURN_IF(dev_alloc((void**)&h->pp_set, PP_SET_CAP * 16 + 64));
+    if (!h->pp_set) RETURN_IF(h->pp_set.ensure(PP_SET_CAP * 2 + 8));
     u64* out = h->pp_set + 2 * PP_SET_CAP;
     // 1/64 of the rows, between 2^16 and 2^18 samples; the set sized for them (<= 50 % load)
     const u64 ns = std::min<u64>(rows, std::max<u64>(1ULL << 16, std::min<u64>(rows / 64, 1ULL << 18)));
@@ -948,7 +867,7 @@ static int pp_maybe_switch(dbg_agg_handle* h, u32 bid, u64 rows) {
         launch_pp_sample(h->stream, h->dspec, h->dbatches, bid, rows, ns, h->pp_set, set_cap, out);
     }
     HIPCHECK(hipGetLastError());
-    RETURN_IF(ensure_pinned(h, &h->pp_hpart, &h->pp_hpart_cap, 1024));
+    RETURN_IF(h->pp_hpart.ensure_after(h->stream, 1024, 1024));
     HIPCHECK(hipMemcpyAsync(h->pp_hpart, out, 32, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     const double sel = (double)h->pp_hpart[0], D = (double)h->pp_hpart[1], f1 = (double)h->pp_hpart[2];
@@ -978,10 +897,10 @@ static int pp_maybe_switch(dbg_agg_handle* h, u32 bid, u64 rows) {
 // The pinned chunk staging is rewritten only after the stream has drained its last upload.
 static int pp_upload_chunks(dbg_agg_handle* h, const std::vector<PPChunk>& ch, const std::vector<u32>& c0) {
     HIPCHECK(hipStreamSynchronize(h->stream));
-    RETURN_IF(ensure_pinned(h, &h->pp_hchunks, &h->pp_hchunks_cap, ch.size()));
-    RETURN_IF(ensure_pinned(h, &h->pp_hc0, &h->pp_hc0_cap, c0.size()));
-    RETURN_IF(ensure_dev(&h->pp_dchunks, &h->pp_dchunks_cap, ch.size()));
-    RETURN_IF(ensure_dev(&h->pp_dc0, &h->pp_dc0_cap, c0.size()));
+    RETURN_IF(h->pp_hchunks.ensure_after(h->stream, ch.size(), 1024));
+    RETURN_IF(h->pp_hc0.ensure_after(h->stream, c0.size(), 1024));
+    RETURN_IF(h->pp_dchunks.ensure(ch.size(), 64));
+    RETURN_IF(h->pp_dc0.ensure(c0.size(), 64));
     memcpy(h->pp_hchunks, ch.data(), ch.size() * sizeof(PPChunk));
     memcpy(h->pp_hc0, c0.data(), c0.size() * sizeof(u32));
     HIPCHECK(hipMemcpyAsync(h->pp_dchunks, h->pp_hchunks, ch.size() * sizeof(PPChunk), hipMemcpyHostToDevice, h->stream));
@@ -1075,9 +994,9 @@ static int pp_count_scan(dbg_agg_handle* h, int level, int src, int kind, const 
                          bool counted = false, const u16* dig = nullptr) {
     const u64 K = 1ULL << kbits;
     RETURN_IF(pp_upload_chunks(h, ch, c0));
-    if (counted && h->pp_cnt_cap < ch.size() * K) return fail(DBG_ERR_INTERNAL, "fused counts: buffer too small");
-    RETURN_IF(ensure_dev(&h->pp_cnt, &h->pp_cnt_cap, ch.size() * K));
-    RETURN_IF(ensure_dev(&h->pp_off, &h->pp_off_cap, ch.size() * K));
+    if (counted && h->pp_cnt.cap() < ch.size() * K) return fail(DBG_ERR_INTERNAL, "fused counts: buffer too small");
+    RETURN_IF(h->pp_cnt.ensure(ch.size() * K, 64));
+    RETURN_IF(h->pp_off.ensure(ch.size() * K, 64));
     if (!counted) {
         prof::Scope ps(PP_COUNT_NAME[level], h->stream);
         if (F && F->kind)
@@ -1088,7 +1007,7 @@ static int pp_count_scan(dbg_agg_handle* h, int level, int src, int kind, const 
             launch_pp_count(h->stream, h->dspec, h->dbatches, src, kind, recs, h->pp_dchunks, (u32)ch.size(), shift, kbits, h->pp_cnt,
                             (kind ? h->spec.pp_rw_state : h->spec.pp_rw_raw) / 8);
     }
-    RETURN_IF(ensure_dev(&h->pp_scan_tmp, &h->pp_scan_tmp_cap, pp_scan_scratch_words((u32)(c0.size() - 1), kbits)));
+    RETURN_IF(h->pp_scan_tmp.ensure(pp_scan_scratch_words((u32)(c0.size() - 1), kbits), 64));
     {
         prof::Scope ps(PP_SCAN_NAME[level], h->stream);
         launch_pp_scan(h->stream, h->pp_cnt, (u32)ch.size(), kbits, h->pp_dc0, (u32)(c0.size() - 1), h->pp_off, part_out,
@@ -1131,44 +1050,30 @@ static int pp_add_batch(dbg_agg_handle* h, const BatchDesc* st, u32 bid, u64 row
     std::vector<PPChunk> ch;
     for (u64 s = 0; s < rows; s += PP_CHUNK) ch.push_back(PPChunk{s, std::min<u64>(PP_CHUNK, rows - s), bid, 0});
     std::vector<u32> c0{0, (u32)ch.size()};
-    RETURN_IF(ensure_dev(&h->pp_mid, &h->pp_mid_cap, 257));
+    RETURN_IF(h->pp_mid.ensure(257, 64));
     RETURN_IF(pp_count_scan(h, 1, 0, kind, nullptr, ch, c0, 64 - PP_L1_BITS, PP_L1_BITS, h->pp_mid, &F));
-    RETURN_IF(ensure_pinned(h, &h->pp_hpart, &h->pp_hpart_cap, 1024));
+    RETURN_IF(h->pp_hpart.ensure_after(h->stream, 1024, 1024));
     HIPCHECK(hipMemcpyAsync(h->pp_hpart, h->pp_mid, 257 * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     const u64 total = h->pp_hpart[256];
     if (!total) return DBG_OK;
-    if (K.l1_n + total > K.l1_cap) {  // grow (x2), keeping the records already appended
-        const u64 ncap = std::max<u64>(K.l1_n + total, K.l1_n ? 2 * K.l1_cap : 0);
-        u8* nb = nullptr;
-        RETURN_IF(dev_alloc((void**)&nb, ncap * rw + 64));  // slack: the aggregation reads whole words
-        if (K.l1) {
-            if (K.l1_n) HIPCHECK(hipMemcpyAsync(nb, K.l1, K.l1_n * rw, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHECK(hipStreamSynchronize(h->stream));
-            HIPCHECK(hipFree(K.l1));
-        }
-        K.l1 = nb;
-        K.l1_cap = ncap;
+    const u64 l1_cap = pp_rec_cap(K.l1.cap(), rw);
+    if (K.l1_n + total > l1_cap) {  // grow (x2), keeping the records already appended
+        const u64 ncap = std::max<u64>(K.l1_n + total, K.l1_n ? 2 * l1_cap : 0);
+        RETURN_IF(K.l1.grow_keep(ncap * rw + PP_SLACK, K.l1_n * rw, h->stream));
     }
     // the level-2 digits ride along while every record so far has them (fixed-shape raw batches)
     // (EXPERIMENT, DBG_X_PPDIG=0: no digits at all)
     const bool with_dig = F.kind == 1 && kind == 0 && K.dig_n == K.l1_n && !kX_no_dig();
-    if (with_dig && K.l1_n + total > K.dig_cap) {
-        const u64 ncap = std::max<u64>(K.l1_n + total, K.dig_n ? 2 * K.dig_cap : 0);
-        u16* nd = nullptr;
-        RETURN_IF(dev_alloc((void**)&nd, ncap * 2 + 64));
-        if (K.dig) {
-            if (K.dig_n) HIPCHECK(hipMemcpyAsync(nd, K.dig, K.dig_n * 2, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHECK(hipStreamSynchronize(h->stream));
-            HIPCHECK(hipFree(K.dig));
-        }
-        K.dig = nd;
-        K.dig_cap = ncap;
+    const u64 dig_cap = pp_rec_cap(K.dig.cap() * 2, 2);
+    if (with_dig && K.l1_n + total > dig_cap) {
+        const u64 ncap = std::max<u64>(K.l1_n + total, K.dig_n ? 2 * dig_cap : 0);
+        RETURN_IF(K.dig.grow_keep(ncap + PP_SLACK / 2, K.dig_n, h->stream));
     }
     if (with_dig) F.dig = K.dig + K.l1_n;
     RETURN_IF(pp_scatter(h, 1, 0, kind, nullptr, (u32)ch.size(), 64 - PP_L1_BITS, PP_L1_BITS, K.l1 + K.l1_n * rw, &F));
     if (with_dig) K.dig_n = K.l1_n + total;
-    K.segs.push_back(dbg_agg_handle::Seg{K.l1_n, total, std::vector<u64>(h->pp_hpart, h->pp_hpart + 257)});
+    K.segs.push_back(dbg_agg_handle::Seg{K.l1_n, total, std::vector<u64>(h->pp_hpart.get(), h->pp_hpart + 257)});
     K.l1_n += total;
     h->pp_grec_ready = false;
     return DBG_OK;
@@ -1252,16 +1157,9 @@ static int pp_prepare(dbg_agg_handle* h, bool spec_ok) {
         auto& K = h->ppk[kind];
         if (!K.l1_n) continue;
         const u32 rw = kind ? S.pp_rw_state : S.pp_rw_raw;
-        if (K.ab_cap < K.l1_n) {
-            if (K.a) HIPCHECK(hipFree(K.a));
-            if (K.b) HIPCHECK(hipFree(K.b));
-            K.a = K.b = nullptr;
-            K.ab_cap = 0;
-            RETURN_IF(dev_alloc((void**)&K.a, K.l1_n * rw + 64));
-            RETURN_IF(dev_alloc((void**)&K.b, K.l1_n * rw + 64));
-            K.ab_cap = K.l1_n;
-        }
-        RETURN_IF(ensure_dev(&K.part, &K.part_cap, (1ULL << B) + 1));
+        RETURN_IF(K.a.ensure(K.l1_n * rw + PP_SLACK));
+        RETURN_IF(K.b.ensure(K.l1_n * rw + PP_SLACK));
+        RETURN_IF(K.part.ensure((1ULL << B) + 1, 64));
         // level 2: units never straddle a level-1 partition (group = partition index)
         std::vector<PPChunk> ch;
         std::vector<u32> c0;
@@ -1277,7 +1175,7 @@ static int pp_prepare(dbg_agg_handle* h, bool spec_ok) {
         const u32 sh2 = 64 - PP_L1_BITS - k2;
         u64* p2 = k3 ? nullptr : K.part;
         if (k3) {
-            RETURN_IF(ensure_dev(&h->pp_mid, &h->pp_mid_cap, (256ULL << k2) + 1));
+            RETURN_IF(h->pp_mid.ensure((256ULL << k2) + 1, 64));
             p2 = h->pp_mid;
         }
         // the level-2 count reads the digit array (2 bytes per record) when level 1 wrote one
@@ -1289,14 +1187,14 @@ static int pp_prepare(dbg_agg_handle* h, bool spec_ok) {
         // unit (<= PP_CHUNK records): one fewer pass over the records.
         bool fused3 = false;
         if (k3) {
-            RETURN_IF(ensure_pinned(h, &h->pp_hpart, &h->pp_hpart_cap, G2 + 1));
+            RETURN_IF(h->pp_hpart.ensure_after(h->stream, G2 + 1, 1024));
             HIPCHECK(hipMemcpyAsync(h->pp_hpart, p2, (G2 + 1) * 8, hipMemcpyDeviceToHost, h->stream));
             HIPCHECK(hipStreamSynchronize(h->stream));
             u64 mx = 0;
             for (u64 g2 = 0; g2 < G2; ++g2) mx = std::max<u64>(mx, h->pp_hpart[g2 + 1] - h->pp_hpart[g2]);
             fused3 = mx <= PP_CHUNK && ((1u << k2) << k3) <= PP_NEXT_HIST_MAX;
             if (fused3) {
-                RETURN_IF(ensure_dev(&h->pp_cnt, &h->pp_cnt_cap, G2 << k3));
+                RETURN_IF(h->pp_cnt.ensure(G2 << k3, 64));
                 HIPCHECK(hipMemsetAsync(h->pp_cnt, 0, (G2 << k3) * 4, h->stream));
             }
         }
@@ -1329,7 +1227,7 @@ static u64 pp_records(const dbg_agg_handle* h) { return h->ppk[0].l1_n + h->ppk[
 // keys), mode 1 the group records (state record format) into pp_grec.  Totals land in pp_tot.
 static int pp_agg(dbg_agg_handle* h, int mode, const OutDesc* od) {
     const Spec& S = h->spec;
-    if (!h->pp_tot) RETURN_IF(dev_alloc((void**)&h->pp_tot, PPT_WORDS * 8));
+    if (!h->pp_tot) RETURN_IF(h->pp_tot.ensure(PPT_WORDS));
     HIPCHECK(hipMemsetAsync(h->pp_tot, 0, PPT_WORDS * 8, h->stream));
     const u64 N = pp_records(h);
     if (!N) return DBG_OK;
@@ -1359,39 +1257,25 @@ static int pp_agg(dbg_agg_handle* h, int mode, const OutDesc* od) {
     if (mode == 0) {
         o.cols = *od;
     } else {
-        RETURN_IF(ensure_dev(&h->pp_grec, &h->pp_grec_cap, N * S.pp_rw_state));
+        RETURN_IF(h->pp_grec.ensure(N * S.pp_rw_state, 64));
         o.grec = h->pp_grec;
         o.grec_cap = N;
     }
     auto& R = h->ppk[0];
     auto& T = h->ppk[1];
-    if (h->pp_spec >= 0) {
-        // every final partition may spill (skewed keys): room for all their ids (<= 1 MB)
-        const u32 SPILL_CAP = 1u << h->pp_bits;
-        if (h->pp_spill_cap < SPILL_CAP) {
-            if (h->pp_spill) HIPCHECK(hipFree(h->pp_spill));
-            h->pp_spill = nullptr;
-            h->pp_spill_cap = 0;
-            RETURN_IF(dev_alloc((void**)&h->pp_spill, (1 + (size_t)SPILL_CAP) * 4));
-            h->pp_spill_cap = SPILL_CAP;
-        }
+    // every final partition may spill (skewed keys): room for all their ids (<= 1 MB)
+    const u32 SPILL_CAP = 1u << h->pp_bits;
+    if (h->pp_spec >= 0 || h->pp_rc_sub) {
+        RETURN_IF(h->pp_spill.ensure(1 + (u64)SPILL_CAP));
         HIPCHECK(hipMemsetAsync(h->pp_spill, 0, 4, h->stream));
+    }
+    if (h->pp_spec >= 0) {
         prof::Scope ps("pp_agg", h->stream);
         launch_pp_agg_spec(h->stream, S, h->pp_spec, mode, 1u << h->pp_bits, R.part, R.fin, h->pp_spec_sub, o, h->pp_spill, SPILL_CAP);
         // partitions larger than its register budget (skewed keys): the generic kernel, spilled ids only
         launch_pp_agg(h->stream, h->dspec, S, h->dbatches, mode, 1u << h->pp_bits, R.part, nullptr, R.fin, R.alt, nullptr, nullptr,
                       o, h->pp_spill, SPILL_CAP);
     } else if (h->pp_rc_sub) {
-        // every final partition may spill (skewed keys): room for all their ids (<= 1 MB)
-        const u32 SPILL_CAP = 1u << h->pp_bits;
-        if (h->pp_spill_cap < SPILL_CAP) {
-            if (h->pp_spill) HIPCHECK(hipFree(h->pp_spill));
-            h->pp_spill = nullptr;
-            h->pp_spill_cap = 0;
-            RETURN_IF(dev_alloc((void**)&h->pp_spill, (1 + (size_t)SPILL_CAP) * 4));
-            h->pp_spill_cap = SPILL_CAP;
-        }
-        HIPCHECK(hipMemsetAsync(h->pp_spill, 0, 4, h->stream));
         prof::Scope ps("pp_agg", h->stream);
         launch_pp_agg_rc(h->stream, h->dspec, S, h->dbatches, mode, 1u << h->pp_bits, R.part, R.fin, 64 - h->pp_bits - h->pp_rc_sub,
                          h->pp_rc_sub, o, h->pp_spill, SPILL_CAP);
@@ -1400,8 +1284,8 @@ static int pp_agg(dbg_agg_handle* h, int mode, const OutDesc* od) {
                       o, h->pp_spill, SPILL_CAP);
     } else {
         prof::Scope ps("pp_agg", h->stream);
-        launch_pp_agg(h->stream, h->dspec, S, h->dbatches, mode, 1u << h->pp_bits, R.l1_n ? R.part : nullptr,
-                      T.l1_n ? T.part : nullptr, R.fin, R.alt, T.fin, T.alt, o);
+        launch_pp_agg(h->stream, h->dspec, S, h->dbatches, mode, 1u << h->pp_bits, R.l1_n ? R.part.get() : nullptr,
+                      T.l1_n ? T.part.get() : nullptr, R.fin, R.alt, T.fin, T.alt, o);
     }
     HIPCHECK(hipGetLastError());
     return DBG_OK;
@@ -1413,7 +1297,7 @@ static int pp_grec_build(dbg_agg_handle* h) {
     RETURN_IF(pp_agg(h, 1, nullptr));
     const u64 N = std::max<u64>(pp_records(h), 1);
     h->pp_nb = pp_grec_blocks(N);
-    RETURN_IF(ensure_dev(&h->pp_blk, &h->pp_blk_cap, (u64)S.n_keys * h->pp_nb + 8));
+    RETURN_IF(h->pp_blk.ensure((u64)S.n_keys * h->pp_nb + 8, 64));
     if (S.has_strings && pp_records(h)) {
         launch_pp_grec_lengths(h->stream, h->dspec, h->pp_grec, h->pp_tot, h->pp_blk, h->pp_nb, h->dbatches);
         for (int c = 0; c < S.n_keys; ++c)
@@ -1425,7 +1309,7 @@ static int pp_grec_build(dbg_agg_handle* h) {
 }
 
 static int pp_read_tot(dbg_agg_handle* h) {
-    if (!h->pp_htot) HIPCHECK(hipHostMalloc((void**)&h->pp_htot, PPT_WORDS * 8, hipHostMallocDefault));
+    if (!h->pp_htot) RETURN_IF(h->pp_htot.ensure(PPT_WORDS));
     HIPCHECK(hipMemcpyAsync(h->pp_htot, h->pp_tot, PPT_WORDS * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     h->pp_stat_rounds = h->pp_htot[PPT_ROUNDS];
@@ -1613,13 +1497,6 @@ int dbg_agg_set_host_staging(dbg_agg_handle* h, uint64_t rows) {
     return DBG_OK;
 }
 
-static int ensure_buf(u64** p, u64* cap, u64 n) {
-    if (n <= *cap) return DBG_OK;
-    if (*p) HIPCHECK(hipFree(*p));
-    *cap = std::max<u64>(n, 1024);
-    return dev_alloc((void**)p, *cap * 8);
-}
-
 // Payload bytes of every String MIN/MAX result column (h->agg_string_bytes): one pass over the
 // table's groups that follows each state's row reference to its length.
 static int str_agg_totals(dbg_agg_handle* h) {
@@ -1627,8 +1504,8 @@ static int str_agg_totals(dbg_agg_handle* h) {
     if (!has_str_minmax(S)) return DBG_OK;
     h->agg_string_bytes.assign(S.n_aggs, 0);
     if (h->n_groups == 0) return DBG_OK;
-    u64* dtot = nullptr;
-    RETURN_IF(dev_alloc((void**)&dtot, 8ull * S.n_aggs));
+    Buf<u64> dtot;
+    RETURN_IF(dtot.ensure(S.n_aggs));
     hipError_t e = hipMemsetAsync(dtot, 0, 8ull * S.n_aggs, h->stream);
     if (e == hipSuccess) {
         prof::Scope ps("str_agg_bytes", h->stream);
@@ -1636,7 +1513,6 @@ static int str_agg_totals(dbg_agg_handle* h) {
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h->agg_string_bytes.data(), dtot, 8ull * S.n_aggs, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(dtot);
     if (e != hipSuccess) return fail(DBG_ERR_DEVICE, std::string("string aggregate sizes: ") + hipGetErrorString(e));
     return DBG_OK;
 }
@@ -1660,8 +1536,8 @@ int dbg_agg_finalize(dbg_agg_handle* h, uint64_t* n_groups, uint64_t* string_byt
     // (resolve_overflow) and the count run again.
     for (int round = 0; round < 3; ++round) {
         u64 nb = finalize_blocks(h->cap);
-        RETURN_IF(ensure_buf(&h->d_pos, &h->pos_cap, nb + 16));
-        RETURN_IF(ensure_buf(&h->d_str_pos, &h->str_pos_cap, (u64)S.n_keys * nb + 8));
+        RETURN_IF(h->d_pos.ensure(nb + 16, 1024));
+        RETURN_IF(h->d_str_pos.ensure((u64)S.n_keys * nb + 8, 1024));
         TableDesc t = table_desc(h);
         {
             prof::Scope ps("count_groups", h->stream);
@@ -1773,14 +1649,13 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
             }
         return DBG_OK;
     }
-    std::vector<void*> temps;
+    std::vector<DevBuf> temps;  // freed on every way out
     auto tmp = [&](size_t bytes, void** p) -> int {
-        RETURN_IF(dev_alloc(p, bytes));
-        temps.push_back(*p);
+        DevBuf b;
+        RETURN_IF(b.ensure(bytes));
+        *p = b.get();
+        temps.push_back(std::move(b));
         return DBG_OK;
-    };
-    auto free_temps = [&]() {
-        for (void* p : temps) hipFree(p);
     };
     OutDesc od;
     memset(&od, 0, sizeof(od));
@@ -1816,10 +1691,7 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
             else rc = tmp(n, (void**)&od.agg_valid[a]);
         }
     }
-    if (rc != DBG_OK) {
-        free_temps();
-        return rc;
-    }
+    RETURN_IF(rc);
     if (h->pp) {
         prof::Scope ps("pp_write", h->stream);
         launch_pp_grec_write(h->stream, h->dspec, h->dbatches, h->pp_grec, h->pp_tot, h->pp_blk, h->pp_nb, od,
@@ -1839,10 +1711,7 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
         if (t.nullable) {
             u8* bits = nullptr;
             if (on_device) bits = out_keys[c].validity;
-            else if (tmp((n + 7) / 8, (void**)&bits) != DBG_OK) {
-                free_temps();
-                return DBG_ERR_OOM;
-            }
+            else if (tmp((n + 7) / 8, (void**)&bits) != DBG_OK) return DBG_ERR_OOM;
             if (bits) launch_pack_bits(h->stream, od.key_valid[c], n, bits);
             if (!on_device && out_keys[c].validity)
                 hipMemcpyAsync(out_keys[c].validity, bits, (n + 7) / 8, hipMemcpyDeviceToHost, h->stream);
@@ -1851,10 +1720,7 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
     std::vector<u64> ser_tot(S.n_aggs, 0);
     u64* dser_tot = nullptr;
     if (ser) {
-        if (tmp(8ull * S.n_aggs, (void**)&dser_tot) != DBG_OK) {
-            free_temps();
-            return DBG_ERR_OOM;
-        }
+        if (tmp(8ull * S.n_aggs, (void**)&dser_tot) != DBG_OK) return DBG_ERR_OOM;
         for (int a = 0; a < S.n_aggs; ++a) {
             u64* offs = nullptr;
             u8* data = nullptr;
@@ -1862,7 +1728,6 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
                 offs = out_aggs[a].offsets;
                 data = (u8*)out_aggs[a].data;
             } else if (tmp((n + 1) * 8, (void**)&offs) != DBG_OK || tmp(n * od.ser_stride[a], (void**)&data) != DBG_OK) {
-                free_temps();
                 return DBG_ERR_OOM;
             }
             launch_ser_compact(h->stream, od.agg_valid[a], (const u8*)od.agg_data[a], od.ser_stride[a], n, offs, data, dser_tot + a);
@@ -1888,12 +1753,9 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
         if (on_device) {
             offs = out_aggs[a].offsets;
             data = (u8*)out_aggs[a].data;
-            if (!offs || (total && !data)) {
-                free_temps();
+            if (!offs || (total && !data))
                 return fail(DBG_ERR_INVALID, "dbg_agg_result: a String aggregate needs offsets and data buffers");
-            }
         } else if (tmp((n + 1) * 8, (void**)&offs) != DBG_OK || tmp(total, (void**)&data) != DBG_OK) {
-            free_temps();
             return DBG_ERR_OOM;
         }
         {
@@ -1910,10 +1772,7 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
         if (t.nullable) {
             u8* bits = nullptr;
             if (on_device) bits = out_aggs[a].validity;
-            else if (tmp((n + 7) / 8, (void**)&bits) != DBG_OK) {
-                free_temps();
-                return DBG_ERR_OOM;
-            }
+            else if (tmp((n + 7) / 8, (void**)&bits) != DBG_OK) return DBG_ERR_OOM;
             if (bits && od.agg_valid[a]) launch_pack_bits(h->stream, od.agg_valid[a], n, bits);
             else if (bits) launch_fill_valid(h->stream, n, bits);
             if (!on_device && out_aggs[a].validity)
@@ -1933,8 +1792,7 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
                 hipMemcpyAsync(out_aggs[a].data, od.agg_data[a], n * type_width(h->result_types[a].type), hipMemcpyDeviceToHost, h->stream);
     }
     HIPCHECK(hipMemcpyAsync(h->hcounters, h->counters, CNT_WORDS * 8, hipMemcpyDeviceToHost, h->stream));
-    hipError_t e = hipStreamSynchronize(h->stream);
-    free_temps();
+    hipError_t e = hipStreamSynchronize(h->stream);  // nothing reads the temporaries past it
     if (e != hipSuccess) return fail(DBG_ERR_DEVICE, std::string("result: ") + hipGetErrorString(e));
     if (h->hcounters[CNT_ERR] & ERR_DEC_OVERFLOW) {
         HIPCHECK(hipMemsetAsync(h->counters + CNT_ERR, 0, 8, h->stream));
@@ -2006,7 +1864,7 @@ static int pp_fin_launch(dbg_agg_handle* h, const OutDesc& od) {
         }
     }
     launch_finish_outputs(h->stream, od, h->pp_tot, S.n_keys, S.n_aggs);
-    if (!h->pp_htot) HIPCHECK(hipHostMalloc((void**)&h->pp_htot, PPT_WORDS * 8, hipHostMallocDefault));
+    if (!h->pp_htot) RETURN_IF(h->pp_htot.ensure(PPT_WORDS));
     HIPCHECK(hipMemcpyAsync(h->pp_htot, h->pp_tot, PPT_WORDS * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipGetLastError());
     return DBG_OK;
@@ -2046,8 +1904,8 @@ static int fin_launch(dbg_agg_handle* h) {
     const Spec& S = h->spec;
     RETURN_IF(stage_flush(h));  // staged host rows first (this launches any held-back insert)
     u64 nb = finalize_blocks(h->cap);
-    RETURN_IF(ensure_buf(&h->d_pos, &h->pos_cap, nb + 16));
-    RETURN_IF(ensure_buf(&h->d_str_pos, &h->str_pos_cap, (u64)S.n_keys * nb + 8));
+    RETURN_IF(h->d_pos.ensure(nb + 16, 1024));
+    RETURN_IF(h->d_str_pos.ensure((u64)S.n_keys * nb + 8, 1024));
     // the held-back partitioned insert's table stage writes the result columns directly (one
     // non-nullable integer key, COUNT(*): what part_slice_bits admits; the table stays empty)
     const bool direct = h->def_part && !h->pp && S.n_keys == 1 && S.n_aggs == 1 && !S.key_types[0].nullable &&
@@ -2055,7 +1913,7 @@ static int fin_launch(dbg_agg_handle* h) {
                         type_width(S.key_types[0].type) == (u32)h->def_part_kw;
     if (direct) {
         h->def_part = false;
-        RETURN_IF(ensure_buf(&h->part_status, &h->part_status_cap, part_direct_status_words(h->cap, h->def_part_sb)));
+        RETURN_IF(h->part_status.ensure(part_direct_status_words(h->cap, h->def_part_sb), 1024));
     }
     TableDesc t = direct ? TableDesc{} : table_desc(h);
     const bool small = h->cap + 1 <= FIN_SMALL_SLOTS;
@@ -2138,7 +1996,7 @@ static int fin_launch(dbg_agg_handle* h) {
             const bool co = S.n_aggs == 1 && S.aggs[0].kind == DBG_AGG_COUNT && S.aggs[0].arg_type < 0 && S.aggs[0].w0 == 1;
             if (dense_on && kw && co && h->def_clean && S.n_keys == 1) {
                 if (!h->dense) {
-                    RETURN_IF(dev_alloc((void**)&h->dense, (65536 + 1024) * 8));
+                    RETURN_IF(h->dense.ensure(65536 + 1024));
                     HIPCHECK(hipMemsetAsync(h->dense, 0, (65536 + 1024) * 8, h->stream));
                 }
                 ff.dense = h->dense;
@@ -2316,11 +2174,7 @@ static int fin_setup(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_column
     for (int c = 0; c < S.n_keys; ++c) n_nullable += S.key_types[c].nullable ? 1 : 0;
     for (int a = 0; a < S.n_aggs; ++a) n_nullable += h->result_types[a].nullable ? 1 : 0;
     u64 need = (u64)n_nullable * (max_groups + 1);
-    if (need > h->vbytes_cap) {
-        if (h->vbytes) HIPCHECK(hipFree(h->vbytes));
-        h->vbytes_cap = std::max<u64>(need, 4096);
-        RETURN_IF(dev_alloc((void**)&h->vbytes, h->vbytes_cap));
-    }
+    if (need > h->vbytes.cap()) RETURN_IF(h->vbytes.ensure(need, 4096));
     return DBG_OK;
 }
 
@@ -2438,24 +2292,24 @@ int dbg_agg_partition(dbg_agg_handle* h, uint32_t n_parts, int scheme, uint64_t*
     const bool prefix = scheme != 2 && h->part_keys > 0 && h->part_keys < S.n_keys;
     if (prefix && h->pp) return fail(DBG_ERR_UNSUPPORTED, "partition keys: table strategy only");
     if (prefix && n_parts > 1) {  // buckets of the first part_keys key columns' group hash, per slot
-        RETURN_IF(ensure_buf(&h->d_lpart, &h->lpart_cap, (h->cap + 1) / 2 + 1));
+        RETURN_IF(h->d_lpart.ensure((h->cap + 1) / 2 + 1, 1024));
         prof::Scope ps("prefix_bucket", h->stream);
-        launch_prefix_slot_bucket(h->stream, h->dspec, h->dbatches, table_desc(h), h->part_keys, n_parts, scheme, (u32*)h->d_lpart);
-        lpart = (const u32*)h->d_lpart;
+        launch_prefix_slot_bucket(h->stream, h->dspec, h->dbatches, table_desc(h), h->part_keys, n_parts, scheme, (u32*)h->d_lpart.get());
+        lpart = (const u32*)h->d_lpart.get();
         scheme = 2;  // count and export read lpart
     }
     if (scheme == 2 && n_parts > 1 && !prefix) {  // hash2bucket<bits, true> of each group's FastHash
         const u64 n = h->pp ? h->n_groups : h->cap + 1;
-        RETURN_IF(ensure_buf(&h->d_lpart, &h->lpart_cap, n / 2 + 1));
+        RETURN_IF(h->d_lpart.ensure(n / 2 + 1, 1024));
         prof::Scope ps("legacy_bucket", h->stream);
-        if (h->pp) launch_pp_grec_legacy_bucket(h->stream, h->dspec, h->dbatches, h->pp_grec, h->n_groups, L, (u32*)h->d_lpart);
-        else launch_legacy_slot_bucket(h->stream, h->dspec, h->dbatches, table_desc(h), L, (u32*)h->d_lpart);
-        lpart = (const u32*)h->d_lpart;
+        if (h->pp) launch_pp_grec_legacy_bucket(h->stream, h->dspec, h->dbatches, h->pp_grec, h->n_groups, L, (u32*)h->d_lpart.get());
+        else launch_legacy_slot_bucket(h->stream, h->dspec, h->dbatches, table_desc(h), L, (u32*)h->d_lpart.get());
+        lpart = (const u32*)h->d_lpart.get();
     }
     u64 nflat = (u64)n_parts * nb;
-    RETURN_IF(ensure_buf(&h->d_part_pos, &h->part_cap, nflat + 8));
-    RETURN_IF(ensure_buf(&h->d_part_str_pos, &h->part_str_cap, nflat * S.n_keys + 8));
-    if (!h->d_part_str_base) RETURN_IF(dev_alloc((void**)&h->d_part_str_base, 257 * 8));
+    RETURN_IF(h->d_part_pos.ensure(nflat + 8, 1024));
+    RETURN_IF(h->d_part_str_pos.ensure(nflat * S.n_keys + 8, 1024));
+    if (!h->d_part_str_base) RETURN_IF(h->d_part_str_base.ensure(257));
     HIPCHECK(hipMemsetAsync(h->d_part_str_pos, 0, (nflat * S.n_keys + 8) * 8, h->stream));
     {
         prof::Scope ps("count_groups", h->stream);
@@ -2501,10 +2355,10 @@ int dbg_agg_export_records(dbg_agg_handle* h, void* dev_records, void* dev_strin
     prof::Scope ps("export_records", h->stream);
     if (h->pp)
         launch_pp_grec_export(h->stream, h->dspec, h->dbatches, h->pp_grec, h->n_groups, h->part_n, h->part_scheme,
-                              (const u32*)h->d_lpart, h->d_part_pos, h->d_part_str_pos, h->part_nb, (u8*)dev_records,
+                              (const u32*)h->d_lpart.get(), h->d_part_pos, h->d_part_str_pos, h->part_nb, (u8*)dev_records,
                               (u8*)dev_strings, h->d_part_str_base);
     else
-        launch_export(h->stream, h->dspec, h->spec, h->dbatches, table_desc(h), h->part_n, h->part_scheme, (const u32*)h->d_lpart,
+        launch_export(h->stream, h->dspec, h->spec, h->dbatches, table_desc(h), h->part_n, h->part_scheme, (const u32*)h->d_lpart.get(),
                       h->d_part_pos, h->d_part_str_pos, (u8*)dev_records, (u8*)dev_strings, h->d_part_str_base);
     HIPCHECK(hipGetLastError());
     return DBG_OK;
@@ -2663,11 +2517,9 @@ int dbg_agg_compact(dbg_agg_handle* h, int* compacted) {
     u64 n = 0, sb = 0;
     RETURN_IF(dbg_agg_partition(h, 1, 0, &n, &sb));
     DevBuf rb, strb;
-    rb.bytes = std::max<u64>(n * S.rec_width, 16);
-    strb.bytes = std::max<u64>(sb, 16);
-    RETURN_IF(dev_alloc(&rb.p, rb.bytes));
-    int rc = dev_alloc(&strb.p, strb.bytes);
-    if (rc == DBG_OK) rc = dbg_agg_export_records(h, rb.p, strb.p);
+    RETURN_IF(rb.ensure(n * S.rec_width, 16));
+    int rc = strb.ensure(sb, 16);
+    if (rc == DBG_OK) rc = dbg_agg_export_records(h, rb, strb);
     if (rc == DBG_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(DBG_ERR_DEVICE, "compact: export failed");
     // the handle keeps its strategy: the re-merged batch (one record per group) must not be
     // probed again — on an AUTO handle with many groups the probe would see ratio ~1 and switch
@@ -2676,18 +2528,15 @@ int dbg_agg_compact(dbg_agg_handle* h, int* compacted) {
     if (rc == DBG_OK) rc = dbg_agg_reset(h);  // frees the copies of earlier inputs
     h->table_rows = rows_before ? rows_before : 1;
     h->remerged = remerged_before + n;  // merge_record_batch below counts the n records as rows
-    if (rc != DBG_OK) {
-        hipFree(rb.p);
-        if (strb.p) hipFree(strb.p);
-        return rc;
-    }
-    h->owned.push_back(rb);
-    h->owned.push_back(strb);
+    RETURN_IF(rc);
+    const u8* recs = rb;
+    const u8* per_col[DBG_MAX_KEYS];
+    for (int c = 0; c < DBG_MAX_KEYS; ++c) per_col[c] = strb;
+    h->owned.push_back(std::move(rb));
+    h->owned.push_back(std::move(strb));
     h->finalized = false;
     h->clean = false;
-    const u8* per_col[DBG_MAX_KEYS];
-    for (int c = 0; c < DBG_MAX_KEYS; ++c) per_col[c] = (const u8*)strb.p;
-    RETURN_IF(merge_record_batch(h, (const u8*)rb.p, n, per_col));
+    RETURN_IF(merge_record_batch(h, recs, n, per_col));
     if (compacted) *compacted = 1;
     return DBG_OK;
 }
@@ -2697,7 +2546,7 @@ int dbg_agg_compact(dbg_agg_handle* h, int* compacted) {
 int dbg_agg_retained_bytes(dbg_agg_handle* h, uint64_t* bytes) {
     if (!h || !bytes) return fail(DBG_ERR_INVALID, "null argument");
     u64 t = 0;
-    for (const auto& b : h->owned) t += b.bytes;
+    for (const auto& b : h->owned) t += b.cap();
     *bytes = t;
     return DBG_OK;
 }
@@ -2735,15 +2584,13 @@ int dbg_agg_merge_serialized(dbg_agg_handle* h, const dbg_column* state_cols, co
         in.st_offs[a] = d.offsets;
     }
     // records are retained (the table's ref-key entries point at them) until reset
-    DevBuf rb;
-    rb.bytes = rows * S.rec_width;
-    RETURN_IF(dev_alloc(&rb.p, rows * S.rec_width));
-    h->owned.push_back(rb);
-    if (!h->ser_err) RETURN_IF(dev_alloc((void**)&h->ser_err, 8));
+    RETURN_IF(own_alloc(h, rows * S.rec_width));
+    u8* const rb = h->owned.back();
+    if (!h->ser_err) RETURN_IF(h->ser_err.ensure(1));
     HIPCHECK(hipMemsetAsync(h->ser_err, 0, 8, h->stream));
     {
         prof::Scope ps("ser_ingest", h->stream);
-        launch_ser_ingest(h->stream, h->dspec, in, rows, (u8*)rb.p, h->ser_err);
+        launch_ser_ingest(h->stream, h->dspec, in, rows, rb, h->ser_err);
     }
     HIPCHECK(hipGetLastError());
     u64 e = 0;
@@ -2755,7 +2602,7 @@ int dbg_agg_merge_serialized(dbg_agg_handle* h, const dbg_column* state_cols, co
                                          "(OrNull flag 0 or None without a nullable argument)");
     const u8* per_col[DBG_MAX_KEYS];
     for (int c = 0; c < DBG_MAX_KEYS; ++c) per_col[c] = c < S.n_keys ? in.keys[c].data : nullptr;
-    return merge_record_batch(h, (const u8*)rb.p, rows, per_col);
+    return merge_record_batch(h, rb, rows, per_col);
 }
 
 // ---- standalone filter ----
@@ -2769,29 +2616,22 @@ int dbg_filter_select(const dbg_filter* filter, uint64_t rows, uint32_t* sel_out
     memset(&fd, 0, sizeof(fd));
     fd.rows = rows;
     RETURN_IF(fill_filter(&tmp, filter, 1, fd.cols, &fd.n_cols, fd.nodes, &fd.n_nodes));
-    FilterDesc* dfd = nullptr;
-    u64* scratch = nullptr;
+    Buf<FilterDesc> dfd;
+    Buf<u64> scratch;
     u64 nb = filter_blocks(rows);
-    int rc = dev_alloc((void**)&dfd, sizeof(FilterDesc));
-    if (rc == DBG_OK) rc = dev_alloc((void**)&scratch, (nb + 2) * 8);
-    if (rc == DBG_OK) {
-        hipMemcpyAsync(dfd, &fd, sizeof(fd), hipMemcpyHostToDevice, s);
-        {
-            prof::Scope ps("filter_select", s);
-            launch_filter_select(s, dfd, rows, scratch, scratch + nb, sel_out);
-        }
-        u64 tot = 0;
-        if (nb) hipMemcpyAsync(&tot, scratch + nb, 8, hipMemcpyDeviceToHost, s);
-        hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) rc = fail(DBG_ERR_DEVICE, std::string("filter: ") + hipGetErrorString(e));
-        *n_sel = tot;
+    RETURN_IF(dfd.ensure(1));
+    RETURN_IF(scratch.ensure(nb + 2));
+    hipMemcpyAsync(dfd, &fd, sizeof(fd), hipMemcpyHostToDevice, s);
+    {
+        prof::Scope ps("filter_select", s);
+        launch_filter_select(s, dfd, rows, scratch, scratch + nb, sel_out);
     }
-    if (dfd) hipFree(dfd);
-    if (scratch) hipFree(scratch);
-    for (auto& b : tmp.owned) hipFree(b.p);
-    tmp.owned.clear();
-    tmp.stream = nullptr;
-    return rc;
+    u64 tot = 0;
+    if (nb) hipMemcpyAsync(&tot, scratch + nb, 8, hipMemcpyDeviceToHost, s);
+    hipError_t e = hipStreamSynchronize(s);  // the kernel has read dfd, scratch and tmp's constants
+    *n_sel = tot;
+    if (e != hipSuccess) return fail(DBG_ERR_DEVICE, std::string("filter: ") + hipGetErrorString(e));
+    return DBG_OK;
 }
 
 int dbg_take_fixed(const dbg_column* col, const uint32_t* sel, uint64_t n_sel, void* out_data, uint8_t* out_validity, void* stream) {
@@ -2809,12 +2649,11 @@ int dbg_take_fixed(const dbg_column* col, const uint32_t* sel, uint64_t n_sel, v
     d.validity = col->validity;
     d.validity_offset = col->validity_offset;
     d.data_offset = col->data_offset;
-    u8* vbytes = nullptr;
-    if (out_validity && col->dt.nullable) RETURN_IF(dev_alloc((void**)&vbytes, n_sel + 1));
+    Buf<u8> vbytes;
+    if (out_validity && col->dt.nullable) RETURN_IF(vbytes.ensure(n_sel + 1));
     launch_take_fixed(s, d, sel, n_sel, (u8*)out_data, vbytes);
     if (vbytes) launch_pack_bits(s, vbytes, n_sel, out_validity);
     HIPCHECK(hipStreamSynchronize(s));
-    if (vbytes) hipFree(vbytes);
     return DBG_OK;
 }
 
@@ -2826,14 +2665,13 @@ int dbg_take_string(const dbg_column* col, const uint32_t* sel, uint64_t n_sel, 
     launch_take_string_offsets(s, col->offsets, sel, n_sel, out_offsets);
     // n_sel lengths + one zero -> exclusive scan -> n_sel + 1 offsets; the total lands in a pinned word
     HIPCHECK(hipMemsetAsync(out_offsets + n_sel, 0, 8, s));
-    u64* dtot = nullptr;
-    RETURN_IF(dev_alloc((void**)&dtot, 8));
+    Buf<u64> dtot;
+    RETURN_IF(dtot.ensure(1));
     u64 total = 0;
     hipError_t e = hipMemsetAsync(dtot, 0, 8, s);
     if (e == hipSuccess && n_sel) launch_exclusive_scan(s, out_offsets, n_sel + 1, dtot);
     if (e == hipSuccess) e = hipMemcpyAsync(&total, dtot, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    hipFree(dtot);
     if (e != hipSuccess) return fail(DBG_ERR_DEVICE, hipGetErrorString(e));
     *total_bytes = total;
     if (total > data_cap) return fail(DBG_ERR_INVALID, "dbg_take_string: data buffer too small (*total_bytes needed)");
@@ -2847,12 +2685,11 @@ int dbg_take_string(const dbg_column* col, const uint32_t* sel, uint64_t n_sel, 
     d.offsets = col->offsets;
     d.validity = col->validity;
     d.validity_offset = col->validity_offset;
-    u8* vbytes = nullptr;
-    if (out_validity && col->dt.nullable) RETURN_IF(dev_alloc((void**)&vbytes, n_sel + 1));
+    Buf<u8> vbytes;
+    if (out_validity && col->dt.nullable) RETURN_IF(vbytes.ensure(n_sel + 1));
     launch_take_string_bytes(s, d, sel, n_sel, out_offsets, (u8*)out_data, vbytes);
     if (vbytes) launch_pack_bits(s, vbytes, n_sel, out_validity);
     HIPCHECK(hipStreamSynchronize(s));
-    if (vbytes) hipFree(vbytes);
     return DBG_OK;
 }
 

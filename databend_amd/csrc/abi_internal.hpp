@@ -14,6 +14,7 @@
 #include <chrono>
 
 #include "agg.hpp"
+#include "dev_buf.hpp"
 #include "host_stage.hpp"
 #include "legacy.hpp"
 #include "serde.hpp"
@@ -42,10 +43,9 @@ int fail(int code, const std::string& msg);
 // ------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
+// Every buffer a handle owns is a Buf member (dev_buf.hpp), freed with the handle: a member that
+// is a raw pointer aliases memory owned elsewhere and says so.
+using DevBuf = Buf<u8>;  // device bytes; cap() = bytes
 
 struct FinState {
     bool active = false;
@@ -59,18 +59,23 @@ struct FinState {
     bool direct = false;  // the held-back partitioned insert's direct stage wrote the results (part_slice_direct)
 };
 
+// A record buffer of the partitioned payload ends in PP_SLACK bytes the records do not use (the
+// aggregation reads whole words): the records of `rw` bytes a buffer of `cap` bytes holds.
+constexpr u64 PP_SLACK = 64;
+inline u64 pp_rec_cap(u64 cap, u64 rw) { return cap > PP_SLACK ? (cap - PP_SLACK) / rw : 0; }
+
 struct dbg_agg_handle {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     Spec spec{};
-    Spec* dspec = nullptr;
+    Buf<Spec> dspec;
     std::vector<dbg_datatype> result_types;
     std::vector<int> src_kinds;  // dbg_agg_kind as created (AVG_SQL is stored as AVG)
     bool partial = true;
 
     // table
-    u64* slots = nullptr;
-    u64 cap = 0;
+    Buf<u64> slots;
+    u64 cap = 0;       // slots of the table (the buffer holds cap + 1)
     u64 init_cap = 0;  // from the capacity hint: the table never shrinks below it
     // An on-device fast-path insert whose launch is held back until the next call: a
     // finalize_into_async of a small table then runs in the same launch (FusedFin); any other
@@ -80,30 +85,26 @@ struct dbg_agg_handle {
     u32 def_bid = 0;
     u64 def_rows = 0;
     BatchDesc def_hb;
-    u64* counters = nullptr;   // device, CNT_WORDS
-    u64* hcounters = nullptr;  // pinned
-    u64* hcounters_dev = nullptr;  // its device mapping (finalize_small writes it directly)
-    u64* dense = nullptr;          // fused_dense's direct-mapped counts + presence bitmap (zero between launches)
-    // overflow lists (deferred)
-    u64* ovf_rows = nullptr;
-    u64 ovf_rows_cap = 0;
-    u64* ovf_recs = nullptr;
-    u64 ovf_recs_cap = 0;
+    Buf<u64> counters;             // device, CNT_WORDS
+    Buf<u64, MappedMem> hcounters;  // pinned; its tail mirrors what the finalize kernels post
+    u64* hcounters_dev = nullptr;  // alias: its device mapping (finalize_small writes it directly)
+    Buf<u64> dense;                // fused_dense's direct-mapped counts + presence bitmap (zero between launches)
+    // overflow lists (deferred): rows, and records of tstride words
+    Buf<u64> ovf_rows, ovf_recs;
     u64 pending_rows = 0, pending_recs = 0;
     // parking rows of per-workgroup partial tables (TableDesc::scratch)
-    u64* scratch = nullptr;
+    Buf<u64> scratch;
     u32 scr_blocks = 0;
 
     // batches (ids 1..n_batches); descs in device memory, staged through pinned memory
-    BatchDesc* dbatches = nullptr;
-    u64 batch_cap = 0;
+    Buf<BatchDesc> dbatches;
     u32 n_batches = 0;
     // descriptor cache: ids 1..n_cached hold immutable descriptors of device-resident inputs
     // (pointers only), kept across dbg_agg_reset so a re-submitted batch needs no upload
     u32 n_cached = 0;
     std::vector<std::pair<u64, BatchDesc>> desc_cache;  // (content hash, host copy); index = id - 1
-    std::vector<BatchDesc*> pinned_descs;   // pinned staging desc per batch id (pooled)
-    std::vector<BatchDesc*> pinned_chunks;  // their allocations
+    std::vector<BatchDesc*> pinned_descs;   // alias: pinned staging desc per batch id (pooled)
+    std::vector<PinnedBuf<BatchDesc>> pinned_chunks;  // their allocations
     std::vector<DevBuf> owned;             // device copies of host inputs / filter constants
     // before_merge exchange receive buffers (records, string blobs) when this is the final table:
     // kept across resets and grown only, so a step allocates nothing; `xrecv_busy` while the table
@@ -117,7 +118,7 @@ struct dbg_agg_handle {
     // transfer may still be writing.
     struct XChunk {
         std::vector<u64> pc;  // [n][2][P] counts of the chunk, every source
-        const void* recv[2] = {nullptr, nullptr};
+        const void* recv[2] = {nullptr, nullptr};  // alias: the communicator's slots
     };
     std::vector<XChunk> xchunks;
     u32 xfirst[2] = {0, 0};
@@ -127,24 +128,18 @@ struct dbg_agg_handle {
     u64 n_groups = 0;
     std::vector<u64> string_bytes;
     std::vector<u64> agg_string_bytes;  // payload bytes of each String MIN/MAX result column (dbg_agg_finalize)
-    u64* d_pos = nullptr;     // scanned per-block group counts
-    u64* d_str_pos = nullptr;  // [n_keys][blocks] scanned per column
-    u64 pos_cap = 0, str_pos_cap = 0;
+    Buf<u64> d_pos;      // scanned per-block group counts
+    Buf<u64> d_str_pos;  // [n_keys][blocks] scanned per column
     // partition state
     u32 part_n = 0;
     int part_scheme = 0;
     int part_keys = 0;  // dbg_agg_set_partition_keys: buckets by the first part_keys key columns (0 = all)
     u64 part_nb = 0;  // blocks of the partition histogram
-    u64* d_part_pos = nullptr;
-    u64* d_part_str_pos = nullptr;
-    u64* d_part_str_base = nullptr;
-    u64 part_cap = 0, part_str_cap = 0;
-    u64* d_lpart = nullptr;   // scheme 2: legacy bucket per slot / group record (u32)
-    u64 lpart_cap = 0;
+    Buf<u64> d_part_pos, d_part_str_pos, d_part_str_base;
+    Buf<u64> d_lpart;  // scheme 2: legacy bucket per slot / group record (u32)
     std::vector<u64> part_counts, part_strings;
     // fused finalize: validity bytes staging
-    u8* vbytes = nullptr;
-    u64 vbytes_cap = 0;
+    Buf<u8> vbytes;
     // fused finalize in flight (dbg_agg_finalize_into_async)
     FinState fin;
     hipEvent_t switch_ev = nullptr;  // dbg_agg_set_stream hand-off
@@ -158,12 +153,8 @@ struct dbg_agg_handle {
     u64 fin_seq = 0;              // sequence number the finalize kernel posts to host_mirror
     bool uploads_pending = false; // descriptor uploads from pinned staging since the last sync
     // radix-partitioned insert (part.hip): sorted mixed keys, slice bounds, rocPRIM scratch
-    u64* part_sorted = nullptr;
-    u64 part_sorted_cap = 0;
-    u64* part_bounds = nullptr;
-    u64 part_bounds_cap = 0;
-    void* part_temp = nullptr;
-    size_t part_temp_cap = 0;
+    Buf<u64> part_sorted, part_bounds;
+    Buf<u8> part_temp;
     // A partitioned insert into an empty table in recycle mode holds back its table stage (the
     // keys are sorted already): a finalize_into that comes next runs the direct stage instead —
     // groups into the result columns without the table-wide count and write passes, the slots used
@@ -172,8 +163,7 @@ struct dbg_agg_handle {
     bool def_part = false;
     u32 def_part_sb = 0;
     int def_part_kw = 0;
-    u64* part_status = nullptr;  // the direct stage's look-back words
-    u64 part_status_cap = 0;
+    Buf<u64> part_status;  // the direct stage's look-back words
     u64 table_rows = 0;  // rows / records inserted into the HBM table since the last reset
     u64 remerged = 0;    // of which records dbg_agg_compact merged back (groups, not input rows)
     int strategy = DBG_STRATEGY_AUTO;
@@ -193,56 +183,43 @@ struct dbg_agg_handle {
         std::vector<u64> off;  // level-1 partition offsets (257), relative to base
     };
     struct Kind {  // 0: raw records (add_groups), 1: state records (merge_records)
-        u8* l1 = nullptr;
-        u64 l1_cap = 0, l1_n = 0;  // records
-        u16* dig = nullptr;        // level-2 digits of records [0, dig_n) (fixed-shape raw level 1)
-        u64 dig_cap = 0, dig_n = 0;
+        Buf<u8> l1;
+        u64 l1_n = 0;   // records
+        Buf<u16> dig;   // level-2 digits of records [0, dig_n) (fixed-shape raw level 1)
+        u64 dig_n = 0;
         std::vector<Seg> segs;
-        u8* a = nullptr;  // finalize levels: ping-pong buffers, l1_n records each
-        u8* b = nullptr;
-        u64 ab_cap = 0;
-        u64* part = nullptr;  // final partition offsets (device)
-        u64 part_cap = 0;
-        u8* fin = nullptr;    // final-level buffer and its alternate (the aggregate's overflow)
-        u8* alt = nullptr;
+        Buf<u8> a, b;   // finalize levels: ping-pong buffers of one size, l1_n records each
+        Buf<u64> part;  // final partition offsets (device)
+        u8* fin = nullptr;  // alias: the final-level buffer (a or b) and its alternate (the aggregate's overflow)
+        u8* alt = nullptr;  // alias
     } ppk[2];
     u32 pp_bits = 0;  // final partition bits
     u32 pp_rc_sub = 0;  // > 0: record-centric aggregation in 2^pp_rc_sub rounds per partition (pp.hip)
     int pp_spec = -1;   // >= 0: the compile-time specialised aggregation's shape (pp_agg_spec_kernel)
     u32 pp_spec_sub = 0;  // its rounds per partition: 2^pp_spec_sub
-    u32* pp_spill = nullptr;  // [count, partition ids...] spilled by the specialised / record-centric kernel
-    u64 pp_spill_cap = 0;     // ids it holds: one per final partition, so no spill is ever dropped
-    u32* pp_cnt = nullptr;
-    u64 pp_cnt_cap = 0;
-    u64* pp_off = nullptr;
-    u64 pp_off_cap = 0;
-    u64* pp_scan_tmp = nullptr;  // scan scratch (group totals, block sums)
-    u64 pp_scan_tmp_cap = 0;
-    u64* pp_last_part = nullptr;  // partition offsets of the last count_scan (read by its scatter)
-    u64* pp_mid = nullptr;  // intermediate partition offsets (device)
-    u64 pp_mid_cap = 0;
-    PPChunk* pp_dchunks = nullptr;
-    u64 pp_dchunks_cap = 0;
-    PPChunk* pp_hchunks = nullptr;  // pinned staging
-    u64 pp_hchunks_cap = 0;
-    u32* pp_dc0 = nullptr;
-    u64 pp_dc0_cap = 0;
-    u32* pp_hc0 = nullptr;
-    u64 pp_hc0_cap = 0;
-    u64* pp_hpart = nullptr;  // pinned read-back of partition offsets
-    u64 pp_hpart_cap = 0;
-    u64* pp_tot = nullptr;    // PPT_* (device)
-    u64* pp_htot = nullptr;   // pinned
-    u64* pp_set = nullptr;    // cardinality probe hash set
-    u8* pp_grec = nullptr;    // group records (state record format)
-    u64 pp_grec_cap = 0;      // bytes
-    u64* pp_blk = nullptr;    // per-block string lengths, scanned
-    u64 pp_blk_cap = 0;
+    // [count, partition ids...] spilled by the specialised / record-centric kernel: an id per final
+    // partition, so no spill is ever dropped
+    Buf<u32> pp_spill;
+    Buf<u32> pp_cnt;
+    Buf<u64> pp_off;
+    Buf<u64> pp_scan_tmp;  // scan scratch (group totals, block sums)
+    u64* pp_last_part = nullptr;  // alias: partition offsets of the last count_scan (read by its scatter)
+    Buf<u64> pp_mid;  // intermediate partition offsets (device)
+    Buf<PPChunk> pp_dchunks;
+    PinnedBuf<PPChunk> pp_hchunks;  // staging
+    Buf<u32> pp_dc0;
+    PinnedBuf<u32> pp_hc0;
+    PinnedBuf<u64> pp_hpart;  // read-back of partition offsets
+    Buf<u64> pp_tot;          // PPT_* (device)
+    PinnedBuf<u64> pp_htot;
+    Buf<u64> pp_set;          // cardinality probe hash set
+    Buf<u8> pp_grec;          // group records (state record format)
+    Buf<u64> pp_blk;          // per-block string lengths, scanned
     bool pp_grec_ready = false;
     u64 pp_nb = 0;            // blocks of the grec passes
     u64 pp_stat_rounds = 0;   // partitions that took more than one LDS round (last finalize)
     u64 pp_stat_spilled = 0;  // final partitions handed to the generic kernel (last finalize)
-    u64* ser_err = nullptr;   // serialized-state ingest error bits (serde.hip)
+    Buf<u64> ser_err;         // serialized-state ingest error bits (serde.hip)
 
     // host-block staging (dbg_agg_set_host_staging, host_stage.hpp)
     hstage::Stage stage;
@@ -278,8 +255,7 @@ inline const char* handle_local_reason(const Spec& S) {
             return fail(DBG_ERR_UNSUPPORTED, std::string(what) + ": " + why_);               \
     } while (0)
 
-// handle helpers abi.hip defines for the other units
-int dev_alloc(void** p, size_t bytes);
+// handle helpers abi.hip defines for the other units (dev_alloc: dev_buf.hpp)
 int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtypes);
 // (defined inside abi.hip's extern "C" block; hidden: not part of the library's interface)
 extern "C" __attribute__((visibility("hidden"))) int flush_pending(dbg_agg_handle* h);

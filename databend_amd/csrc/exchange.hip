@@ -67,34 +67,27 @@ RcclApi& rccl_api() {
 struct dbg_comm {
     ncclComm_t comm = nullptr;
     int n = 0, rank = 0, device = 0;
-    u64* dsizes = nullptr;  // device: [2n] own sizes, then [n][2n] gathered
-    u64* hsizes = nullptr;  // pinned mirror of the gathered sizes
-    u8* send_recs = nullptr;
-    u8* send_strs = nullptr;
-    u64 send_recs_cap = 0, send_strs_cap = 0;
+    Buf<u64> dsizes;        // device: [2n] own sizes, then [n][2n] gathered
+    PinnedBuf<u64> hsizes;  // mirror of the gathered sizes
+    Buf<u8> send_recs, send_strs;
     hipEvent_t sent = nullptr;  // the last exchange's sends: the next export into the buffers waits
     bool sent_valid = false;
     hipEvent_t merged = nullptr;  // the final table's stream after a merge: cached receive buffers are reused behind it
     // before-partial payload exchange: send and receive buffers kept between calls (grown only)
-    u8* pay_send = nullptr;
-    u8* pay_recv[2] = {nullptr, nullptr};
-    u64 pay_send_cap = 0, pay_recv_cap[2] = {0, 0};
-    u64* pay_dbuf = nullptr;  // counts all-gather: own row, then n rows
-    u64 pay_dbuf_cap = 0;
+    Buf<u8> pay_send, pay_recv[2];
+    Buf<u64> pay_dbuf;  // counts all-gather: own row, then n rows
     // chunked payload shuffle: transfers on a stream of their own (overlapping the next chunk's
     // level-1 work on the table's stream), two send buffers used in turn
     hipStream_t xs = nullptr;
     hipEvent_t xexp = nullptr;      // the table's stream after a chunk's export
     hipEvent_t xsent[2] = {nullptr, nullptr};
     bool xsent_valid[2] = {false, false};
-    u8* xsend[2] = {nullptr, nullptr};
-    u64 xsend_cap[2] = {0, 0};
+    Buf<u8> xsend[2];
     int xi = 0;
     // receive buffers per chunk slot (records, states), grown only; chunk i of every shuffle lands
     // in slot i.  Receives run on xs, so a slot's next use is stream-ordered behind its last one.
     struct XRecv {
-        u8* p[2] = {nullptr, nullptr};
-        u64 cap[2] = {0, 0};
+        Buf<u8> p[2];
     };
     std::vector<XRecv> xrecv;
 };
@@ -129,7 +122,7 @@ int dbg_comm_create(const uint8_t* id, int n_ranks, int rank, int device, dbg_co
         return fail(DBG_ERR_DEVICE, std::string("ncclCommInitRank: ") + R.ErrorString(r));
     }
     const u64 words = (2ull * n_ranks + 1) * (n_ranks + 1);  // own [2n + 1] sizes + ok word, then n rows
-    if (dev_alloc((void**)&c->dsizes, words * 8) != DBG_OK || hipHostMalloc((void**)&c->hsizes, words * 8, hipHostMallocDefault) != hipSuccess ||
+    if (c->dsizes.ensure(words) != DBG_OK || c->hsizes.ensure(words) != DBG_OK ||
         hipEventCreateWithFlags(&c->sent, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->merged, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->xexp, hipEventDisableTiming) != hipSuccess ||
@@ -150,26 +143,13 @@ void dbg_comm_destroy(dbg_comm* c) {
     if (c->xs) hipStreamSynchronize(c->xs);
     RcclApi& R = rccl_api();
     if (c->comm && R.ok) R.CommDestroy(c->comm);
-    if (c->dsizes) hipFree(c->dsizes);
-    if (c->send_recs) hipFree(c->send_recs);
-    if (c->send_strs) hipFree(c->send_strs);
-    if (c->pay_send) hipFree(c->pay_send);
-    for (int k = 0; k < 2; ++k)
-        if (c->pay_recv[k]) hipFree(c->pay_recv[k]);
-    if (c->pay_dbuf) hipFree(c->pay_dbuf);
-    if (c->hsizes) hipHostFree(c->hsizes);
     if (c->sent) hipEventDestroy(c->sent);
     if (c->merged) hipEventDestroy(c->merged);
-    for (int i = 0; i < 2; ++i) {
-        if (c->xsend[i]) hipFree(c->xsend[i]);
+    for (int i = 0; i < 2; ++i)
         if (c->xsent[i]) hipEventDestroy(c->xsent[i]);
-    }
-    for (auto& x : c->xrecv)
-        for (int k = 0; k < 2; ++k)
-            if (x.p[k]) hipFree(x.p[k]);
     if (c->xexp) hipEventDestroy(c->xexp);
     if (c->xs) hipStreamDestroy(c->xs);
-    delete c;
+    delete c;  // frees every buffer: on the communicator's device, behind the waits above
 }
 
 // ---- before-partial shuffle of the partitioned payload (group_by_shuffle_mode = before_partial,
@@ -253,11 +233,11 @@ static int payload_export_prepare(dbg_agg_handle* h, u32 n_ranks, const u32 firs
                 }
         }
         if (rs.empty()) continue;
-        CopyRange* dr = nullptr;
-        RETURN_IF(dev_alloc((void**)&dr, rs.size() * sizeof(CopyRange)));
-        h->owned.push_back({dr, rs.size() * sizeof(CopyRange)});  // freed at the next reset
+        DevBuf dr;
+        RETURN_IF(dr.ensure(rs.size() * sizeof(CopyRange)));
         HIPCHECK(hipMemcpy(dr, rs.data(), rs.size() * sizeof(CopyRange), hipMemcpyHostToDevice));
-        X.dr[k] = dr;
+        X.dr[k] = (const CopyRange*)dr.get();
+        h->owned.push_back(std::move(dr));  // freed at the next reset
         X.n[k] = (u32)rs.size();
     }
     return DBG_OK;
@@ -328,13 +308,7 @@ static int payload_import_chunks(dbg_agg_handle* h, u32 n_ranks, u32 rank, u32 n
         for (u32 c = 0; c < n_chunks; ++c)
             if (chunk_bytes[c] && !(k ? state[c] : raw[c])) return fail(DBG_ERR_INVALID, "dbg_agg_payload_import: records missing");
         HIPCHECK(hipStreamSynchronize(h->stream));  // the export has read the old payload
-        if (total > K.l1_cap) {
-            if (K.l1) HIPCHECK(hipFree(K.l1));
-            K.l1 = nullptr;
-            K.l1_cap = 0;
-            RETURN_IF(dev_alloc((void**)&K.l1, total * rw + 64));  // slack: the aggregation reads whole words
-            K.l1_cap = total;
-        }
+        if (total > pp_rec_cap(K.l1.cap(), rw)) RETURN_IF(K.l1.ensure(total * rw + PP_SLACK));
         u64 at = 0;
         for (u32 c = 0; c < n_chunks; ++c) {
             if (chunk_bytes[c]) HIPCHECK(hipMemcpyAsync(K.l1 + at, k ? state[c] : raw[c], chunk_bytes[c], hipMemcpyDeviceToDevice, h->stream));
@@ -403,16 +377,7 @@ int dbg_payload_exchange_plan(const dbg_agg_params* params, uint32_t n_ranks, ui
     return DBG_OK;
 }
 
-static int grow_dev(u8** p, u64* cap, u64 need) {
-    if (need <= *cap && *p) return DBG_OK;
-    if (*p) HIPCHECK(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const u64 c = std::max<u64>(need, 1 << 20);
-    RETURN_IF(dev_alloc((void**)p, c));
-    *cap = c;
-    return DBG_OK;
-}
+static const u64 XBUF_FLOOR = 1 << 20;  // bytes: the communicator's send / receive buffers start here
 
 // One all-gather of a per-rank word (every rank calls it): true when every rank passed `ok`.
 // A rank that failed locally after the counts all-gather still takes part in this one, so no peer
@@ -453,13 +418,7 @@ int dbg_agg_exchange_payload(dbg_comm* c, dbg_agg_handle* h, dbg_exchange_stats*
     if (c->sent_valid) HIPCHECK(hipEventSynchronize(c->sent));
     c->sent_valid = false;
     // 1. every rank's counts (and whether it can take part), one all-gather into a cached buffer
-    if (c->pay_dbuf_cap < W * (n + 1)) {
-        if (c->pay_dbuf) HIPCHECK(hipFree(c->pay_dbuf));
-        c->pay_dbuf = nullptr;
-        c->pay_dbuf_cap = 0;
-        RETURN_IF(dev_alloc((void**)&c->pay_dbuf, 8 * W * (n + 1)));
-        c->pay_dbuf_cap = W * (n + 1);
-    }
+    RETURN_IF(c->pay_dbuf.ensure(W * (n + 1)));
     u64* dbuf = c->pay_dbuf;
     std::vector<u64> all(W * n);
     HIPCHECK(hipMemcpyAsync(dbuf, mine.data(), 8 * W, hipMemcpyHostToDevice, s));
@@ -482,8 +441,8 @@ int dbg_agg_exchange_payload(dbg_comm* c, dbg_agg_handle* h, dbg_exchange_stats*
             kind_total[k] += send_bytes[(u64)k * n + d];
             recv_total[k] += recv_bytes[(u64)k * n + d];
         }
-    int rc = grow_dev(&c->pay_send, &c->pay_send_cap, kind_total[0] + kind_total[1]);
-    for (int k = 0; k < 2 && rc == DBG_OK; ++k) rc = grow_dev(&c->pay_recv[k], &c->pay_recv_cap[k], recv_total[k]);
+    int rc = c->pay_send.ensure(kind_total[0] + kind_total[1], XBUF_FLOOR);
+    for (int k = 0; k < 2 && rc == DBG_OK; ++k) rc = c->pay_recv[k].ensure(recv_total[k], XBUF_FLOOR);
     if (rc == DBG_OK) rc = dbg_agg_payload_export(h, n, c->pay_send);
     const std::string local_err = rc == DBG_OK ? std::string() : std::string(dbg_last_error());
     int bad = -1;
@@ -545,14 +504,8 @@ int dbg_agg_exchange_payload_chunk(dbg_comm* c, dbg_agg_handle* h, int last, dbg
     const int rc0 = dbg_agg_payload_counts_from(h, h->xfirst, mine.data(), widths, nseg);
     mine[2 * P] = rc0 == DBG_OK ? 1 : 0;
     // 1. the chunk's counts, every rank's, on the communicator's stream
-    if (c->pay_dbuf_cap < W * (n + 1)) {
-        HIPCHECK(hipStreamSynchronize(xs));
-        if (c->pay_dbuf) HIPCHECK(hipFree(c->pay_dbuf));
-        c->pay_dbuf = nullptr;
-        c->pay_dbuf_cap = 0;
-        RETURN_IF(dev_alloc((void**)&c->pay_dbuf, 8 * W * (n + 1)));
-        c->pay_dbuf_cap = W * (n + 1);
-    }
+    if (c->pay_dbuf.cap() < W * (n + 1)) HIPCHECK(hipStreamSynchronize(xs));
+    RETURN_IF(c->pay_dbuf.ensure(W * (n + 1)));
     u64* dbuf = c->pay_dbuf;
     std::vector<u64> all(W * n);
     HIPCHECK(hipMemcpyAsync(dbuf, mine.data(), 8 * W, hipMemcpyHostToDevice, xs));
@@ -581,7 +534,7 @@ int dbg_agg_exchange_payload_chunk(dbg_comm* c, dbg_agg_handle* h, int last, dbg
         HIPCHECK(hipEventSynchronize(c->xsent[xi]));
         c->xsent_valid[xi] = false;
     }
-    if (kind_total[0] + kind_total[1] > c->xsend_cap[xi]) rc = grow_dev(&c->xsend[xi], &c->xsend_cap[xi], kind_total[0] + kind_total[1]);
+    if (kind_total[0] + kind_total[1] > c->xsend[xi].cap()) rc = c->xsend[xi].ensure(kind_total[0] + kind_total[1], XBUF_FLOOR);
     // this chunk's receive slot: reused as is when large enough (the steady state); a slot that
     // must grow waits for the transfers still queued on xs (an abandoned shuffle's receives)
     const size_t slot = h->xchunks.size();
@@ -589,9 +542,9 @@ int dbg_agg_exchange_payload_chunk(dbg_comm* c, dbg_agg_handle* h, int last, dbg
     auto& XR = c->xrecv[slot];
     for (int k = 0; k < 2 && rc == DBG_OK; ++k)
         if (recv_total[k]) {
-            if (recv_total[k] > XR.cap[k]) {
+            if (recv_total[k] > XR.p[k].cap()) {
                 if (hipStreamSynchronize(xs) != hipSuccess) rc = fail(DBG_ERR_DEVICE, "hipStreamSynchronize");
-                else rc = grow_dev(&XR.p[k], &XR.cap[k], recv_total[k]);
+                else rc = XR.p[k].ensure(recv_total[k], XBUF_FLOOR);
             }
             if (rc == DBG_OK) X.recv[k] = XR.p[k];
         }
@@ -686,23 +639,11 @@ int dbg_merge_exchange_plan(const dbg_agg_params* params, uint32_t n_ranks, uint
 // otherwise a fresh allocation the table owns until its reset.
 static int xrecv_buffer(dbg_agg_handle* fh, int k, u64 bytes, void** out) {
     bytes = std::max<u64>(bytes, 16);
-    if (fh->xrecv_busy) {
-        DevBuf b;
-        b.bytes = bytes;
-        RETURN_IF(dev_alloc(&b.p, bytes));
-        fh->owned.push_back(b);
-        *out = b.p;
-        return DBG_OK;
-    }
-    DevBuf& b = fh->xrecv[k];
-    if (b.bytes < bytes) {
-        if (b.p) HIPCHECK(hipFree(b.p));
-        b.p = nullptr;
-        b.bytes = 0;
-        RETURN_IF(dev_alloc(&b.p, bytes));
-        b.bytes = bytes;
-    }
-    *out = b.p;
+    DevBuf fresh;
+    DevBuf& b = fh->xrecv_busy ? fresh : fh->xrecv[k];
+    RETURN_IF(b.ensure(bytes));
+    *out = b.get();
+    if (fh->xrecv_busy) fh->owned.push_back(std::move(fresh));
     return DBG_OK;
 }
 
@@ -764,8 +705,8 @@ int dbg_agg_exchange(dbg_comm* c, dbg_agg_handle* partial, dbg_agg_handle* final
     }
     if (c->sent_valid) HIPCHECK(hipEventSynchronize(c->sent));
     c->sent_valid = false;
-    rc = grow_dev(&c->send_recs, &c->send_recs_cap, tot_r * w);
-    if (rc == DBG_OK) rc = grow_dev(&c->send_strs, &c->send_strs_cap, tot_s);
+    rc = c->send_recs.ensure(tot_r * w, XBUF_FLOOR);
+    if (rc == DBG_OK) rc = c->send_strs.ensure(tot_s, XBUF_FLOOR);
     if (rc == DBG_OK) rc = dbg_agg_export_records(partial, c->send_recs, c->send_strs);
     if (rc == DBG_OK && (send_b[me] != counts[me] * w || seg_r[me] != counts[me] || seg_s[me] != sbytes[me]))
         rc = fail(DBG_ERR_INTERNAL, "exchange sizes disagree");

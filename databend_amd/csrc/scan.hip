@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "agg.hpp"
+#include "dev_buf.hpp"
 #include "zstd_dev.hpp"
 #include "../../include/dbgpu_scan.h"
 
@@ -972,49 +973,30 @@ int parse_pages(const dbg_parquet_chunk& c, std::vector<HostPage>& out) {
 
 struct dbg_scan_ctx {
     hipStream_t stream = nullptr;
-    u8* chunk = nullptr;  // uploaded chunk bytes
-    u64 chunk_cap = 0;
-    u8* buf = nullptr;
-    u64 buf_cap = 0;
-    ScanPage* pages = nullptr;
-    u64 pages_cap = 0;
-    u8* vbytes = nullptr;
-    u64 vbytes_cap = 0;
-    u32* idx = nullptr;
-    u64 idx_cap = 0;
-    u64* vstart = nullptr;
-    u64 vstart_cap = 0;
-    u32* nwalk = nullptr;
-    u64 nwalk_cap = 0;
-    u64* sptr = nullptr;
-    u64 sptr_cap = 0;
-    u8* bools = nullptr;
-    u64 bools_cap = 0;
-    u64* err = nullptr;  // [0] error bits, [1] string total
-    u64* herr = nullptr; // pinned
-    u8* zlit = nullptr;  // ZSTD literal scratch, ZS_MAX_BLOCK per page
-    u64 zlit_cap = 0;
-    ScanPage* hpages = nullptr;  // pinned staging of the page table (an async upload, not a pageable copy)
-    u64 hpages_cap = 0;
+    Buf<u8> chunk;  // uploaded chunk bytes
+    Buf<u8> buf;
+    Buf<ScanPage> pages;
+    Buf<u8> vbytes;
+    Buf<u32> idx;
+    Buf<u64> vstart;
+    Buf<u32> nwalk;
+    Buf<u64> sptr;
+    Buf<u8> bools;
+    Buf<u64> err;         // [0] error bits, [1] string total
+    PinnedBuf<u64> herr;
+    Buf<u8> zlit;         // ZSTD literal scratch, ZS_MAX_BLOCK per page
+    PinnedBuf<ScanPage> hpages;  // staging of the page table (an async upload, not a pageable copy)
     // native (strawboat) pages: page descriptors and the host-built tables (Bitpacking blocks,
     // String dictionary entries)
-    u8* npg = nullptr;
-    u64 npg_cap = 0;
-    u64* ntab = nullptr;
-    u64 ntab_cap = 0;
+    Buf<u8> npg;
+    Buf<u64> ntab;
 };
 
 namespace {
+// a quarter more than asked for, so chunks of slowly growing sizes do not reallocate each time
 template <typename T>
-int ensure(T** p, u64* cap, u64 n) {
-    if (*cap >= n && *p) return DBG_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const u64 want = n < 64 ? 64 : n + n / 4;
-    if (hipMalloc((void**)p, want * sizeof(T)) != hipSuccess) return abi_fail(DBG_ERR_OOM, "dbg_parquet: device allocation");
-    *cap = want;
-    return DBG_OK;
+int ensure(Buf<T>& b, u64 n) {
+    return b.ensure_alloc(n, n < 64 ? 64 : n + n / 4);
 }
 
 bool target_ok(int ptype, int tlen, const dbg_datatype& t, u32& width) {
@@ -1054,7 +1036,7 @@ int dbg_scan_create(dbg_scan_ctx** out, void* stream) {
     if (!out) return abi_fail(DBG_ERR_INVALID, "dbg_scan_create: null out");
     auto* c = new dbg_scan_ctx();
     c->stream = (hipStream_t)stream;
-    if (hipMalloc((void**)&c->err, 16) != hipSuccess || hipHostMalloc((void**)&c->herr, 16, hipHostMallocDefault) != hipSuccess) {
+    if (c->err.ensure(2) != DBG_OK || c->herr.ensure(2) != DBG_OK) {
         dbg_scan_destroy(c);
         return abi_fail(DBG_ERR_OOM, "dbg_scan_create: allocation");
     }
@@ -1064,11 +1046,6 @@ int dbg_scan_create(dbg_scan_ctx** out, void* stream) {
 
 int dbg_scan_destroy(dbg_scan_ctx* c) {
     if (!c) return DBG_OK;
-    void* dev[] = {c->chunk, c->buf, c->pages, c->vbytes, c->idx, c->vstart, c->nwalk, c->sptr, c->bools, c->err, c->npg, c->ntab};
-    for (void* p : dev)
-        if (p) hipFree(p);
-    if (c->herr) hipHostFree(c->herr);
-    if (c->hpages) hipHostFree(c->hpages);
     delete c;
     return DBG_OK;
 }
@@ -1102,14 +1079,9 @@ int dbg_parquet_decode(dbg_scan_ctx* ctx, const dbg_parquet_chunk* chunk, dbg_da
     SCAN_RET(parse_pages(c, hp));
     // page table, built straight into the pinned staging buffer (every call that uploads from it
     // ends synchronised, so the previous upload has finished reading it)
-    if (ctx->hpages_cap < hp.size() + 2) {
+    if (ctx->hpages.cap() < hp.size() + 2) {
         SCAN_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->hpages) SCAN_HIP(hipHostFree(ctx->hpages));
-        ctx->hpages = nullptr;
-        ctx->hpages_cap = 0;
-        const u64 cap = hp.size() + hp.size() / 2 + 17;
-        SCAN_HIP(hipHostMalloc((void**)&ctx->hpages, cap * sizeof(ScanPage), hipHostMallocDefault));
-        ctx->hpages_cap = cap;
+        SCAN_RET(ctx->hpages.ensure_alloc(hp.size() + 2, hp.size() + hp.size() / 2 + 17));
     }
     // slot 0 stages the zeroed error words (one upload resets them and ships the table)
     memset(ctx->hpages, 0, sizeof(ScanPage));
@@ -1166,25 +1138,25 @@ int dbg_parquet_decode(dbg_scan_ctx* ctx, const dbg_parquet_chunk* chunk, dbg_da
     hipStream_t s = ctx->stream;
     const bool upload = c.device == nullptr;
     if (upload) {
-        SCAN_RET(ensure(&ctx->chunk, &ctx->chunk_cap, c.len + 16));
+        SCAN_RET(ensure(ctx->chunk, c.len + 16));
         SCAN_HIP(hipMemcpyAsync(ctx->chunk, c.host, c.len, hipMemcpyHostToDevice, s));
     }
-    SCAN_RET(ensure(&ctx->buf, &ctx->buf_cap, dst + 16));
-    SCAN_RET(ensure(&ctx->pages, &ctx->pages_cap, n_pages + 2));
-    SCAN_RET(ensure(&ctx->vbytes, &ctx->vbytes_cap, row + 1));
-    SCAN_RET(ensure(&ctx->idx, &ctx->idx_cap, vk + 1));
-    SCAN_RET(ensure(&ctx->nwalk, &ctx->nwalk_cap, n_pages + 1));
+    SCAN_RET(ensure(ctx->buf, dst + 16));
+    SCAN_RET(ensure(ctx->pages, n_pages + 2));
+    SCAN_RET(ensure(ctx->vbytes, row + 1));
+    SCAN_RET(ensure(ctx->idx, vk + 1));
+    SCAN_RET(ensure(ctx->nwalk, n_pages + 1));
     const bool is_str = target.type == DBG_STRING, is_bool = target.type == DBG_BOOLEAN;
     if (is_str) {
-        SCAN_RET(ensure(&ctx->vstart, &ctx->vstart_cap, vk + 1));
-        SCAN_RET(ensure(&ctx->sptr, &ctx->sptr_cap, row + 1));
+        SCAN_RET(ensure(ctx->vstart, vk + 1));
+        SCAN_RET(ensure(ctx->sptr, row + 1));
         if (!out->offsets) return abi_fail(DBG_ERR_INVALID, "dbg_parquet_decode: String output needs offsets");
     }
-    if (is_bool) SCAN_RET(ensure(&ctx->bools, &ctx->bools_cap, row + 1));
-    if (c.codec == DBG_PQ_ZSTD) SCAN_RET(ensure(&ctx->zlit, &ctx->zlit_cap, n_pages * ZS_MAX_BLOCK + 16));
+    if (is_bool) SCAN_RET(ensure(ctx->bools, row + 1));
+    if (c.codec == DBG_PQ_ZSTD) SCAN_RET(ensure(ctx->zlit, n_pages * ZS_MAX_BLOCK + 16));
     if (target.nullable && c.max_def_level && !out->validity && row) return abi_fail(DBG_ERR_INVALID, "dbg_parquet_decode: null validity buffer");
     SCAN_HIP(hipMemcpyAsync(ctx->pages, ctx->hpages, (n_pages + 1) * sizeof(ScanPage), hipMemcpyHostToDevice, s));
-    u64* const perr = (u64*)ctx->pages;
+    u64* const perr = (u64*)ctx->pages.get();
     if (c.physical_type == DBG_PQ_BYTE_ARRAY) SCAN_HIP(hipMemsetAsync(ctx->nwalk, 0, n_pages * 4, s));
     ScanArgs a;
     memset(&a, 0, sizeof(a));
@@ -1914,19 +1886,19 @@ int dbg_native_decode(dbg_scan_ctx* ctx, const dbg_native_column* col, dbg_datat
     hipStream_t s = ctx->stream;
     const bool upload = col->device == nullptr;
     if (upload) {
-        SCAN_RET(ensure(&ctx->chunk, &ctx->chunk_cap, col->len + 16));
+        SCAN_RET(ensure(ctx->chunk, col->len + 16));
         SCAN_HIP(hipMemcpyAsync(ctx->chunk, col->host, col->len, hipMemcpyHostToDevice, s));
     }
-    SCAN_RET(ensure(&ctx->buf, &ctx->buf_cap, P.stage + 16));
-    SCAN_RET(ensure(&ctx->ntab, &ctx->ntab_cap, P.tab.size() + 1));
-    SCAN_RET(ensure(&ctx->npg, &ctx->npg_cap, pages.size() * sizeof(NatPage) + 16));
-    SCAN_RET(ensure(&ctx->vbytes, &ctx->vbytes_cap, row + 1));
+    SCAN_RET(ensure(ctx->buf, P.stage + 16));
+    SCAN_RET(ensure(ctx->ntab, P.tab.size() + 1));
+    SCAN_RET(ensure(ctx->npg, pages.size() * sizeof(NatPage) + 16));
+    SCAN_RET(ensure(ctx->vbytes, row + 1));
     u64 njobs = 0;
     for (int c = 1; c <= 3; ++c) njobs += P.jobs[c].size();
-    SCAN_RET(ensure(&ctx->pages, &ctx->pages_cap, njobs + 1));
-    if (is_str) SCAN_RET(ensure(&ctx->sptr, &ctx->sptr_cap, row + 1));
-    if (is_bool) SCAN_RET(ensure(&ctx->bools, &ctx->bools_cap, row + 8));
-    if (!P.jobs[NC_ZSTD].empty()) SCAN_RET(ensure(&ctx->zlit, &ctx->zlit_cap, (u64)P.jobs[NC_ZSTD].size() * ZS_MAX_BLOCK + 16));
+    SCAN_RET(ensure(ctx->pages, njobs + 1));
+    if (is_str) SCAN_RET(ensure(ctx->sptr, row + 1));
+    if (is_bool) SCAN_RET(ensure(ctx->bools, row + 8));
+    if (!P.jobs[NC_ZSTD].empty()) SCAN_RET(ensure(ctx->zlit, (u64)P.jobs[NC_ZSTD].size() * ZS_MAX_BLOCK + 16));
     // the small tables are copied synchronously from pageable memory (staged by the runtime)
     if (!pages.empty()) SCAN_HIP(hipMemcpyAsync(ctx->npg, pages.data(), pages.size() * sizeof(NatPage), hipMemcpyHostToDevice, s));
     if (!P.tab.empty()) SCAN_HIP(hipMemcpyAsync(ctx->ntab, P.tab.data(), P.tab.size() * 8, hipMemcpyHostToDevice, s));
@@ -1960,7 +1932,7 @@ int dbg_native_decode(dbg_scan_ctx* ctx, const dbg_native_column* col, dbg_datat
     NatBases B;
     B.b[0] = chunk;
     B.b[1] = ctx->buf;
-    B.b[2] = (const u8*)ctx->ntab;
+    B.b[2] = (const u8*)ctx->ntab.get();
     const bool want_vb = col->nullable != 0;
     if (!pages.empty()) {
         // slices per page: ≫ 256 workgroups over the chip, ≥ 1024 rows per slice
@@ -1968,7 +1940,7 @@ int dbg_native_decode(dbg_scan_ctx* ctx, const dbg_native_column* col, dbg_datat
         for (const NatPage& pg : pages) maxn = std::max<u64>(maxn, pg.n);
         u32 split = (u32)std::max<u64>(1, std::min<u64>({16, (4096 + pages.size() - 1) / pages.size(), (maxn + 1023) / 1024}));
         void* ps = prof_scope_begin("nat_decode", s);
-        hipLaunchKernelGGL(nat_decode_kernel, dim3((u32)pages.size(), split), dim3(NAT_NT), 0, s, (const NatPage*)ctx->npg, B,
+        hipLaunchKernelGGL(nat_decode_kernel, dim3((u32)pages.size(), split), dim3(NAT_NT), 0, s, (const NatPage*)ctx->npg.get(), B,
                            is_bool ? ctx->bools : (u8*)out->data, want_vb ? ctx->vbytes : nullptr, ctx->sptr, out->offsets, ctx->err);
         prof_scope_end(ps);
         SCAN_HIP(hipGetLastError());

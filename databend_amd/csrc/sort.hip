@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_buf.hpp"
 #include "device.hpp"
 #include "sort.hpp"
 
@@ -186,13 +187,13 @@ int sort_limit_run(hipStream_t s, const DCol& c, u64 rows, int asc, int nulls_fi
         return DBG_ERR_UNSUPPORTED;
     }
     // one allocation: hist[256] u32 | counter u32 (+pad) | cand_ok | cand_lo | and/or u64 x 2
-    char* buf = nullptr;
+    Buf<char> buf;
     const size_t bytes = 256 * 4 + 16 + 2 * (size_t)SORT_CAP * 8 + 16;
-    if (hipMalloc((void**)&buf, bytes) != hipSuccess) {
+    if (buf.ensure(bytes) != DBG_OK) {
         err = "sort limit: device allocation failed";
         return DBG_ERR_OOM;
     }
-    u32* hist = (u32*)buf;
+    u32* hist = (u32*)buf.get();
     u32* counter = (u32*)(buf + 1024);
     u64* cand_ok = (u64*)(buf + 1024 + 16);
     u64* cand_lo = cand_ok + SORT_CAP;
@@ -295,7 +296,6 @@ int sort_limit_run(hipStream_t s, const DCol& c, u64 rows, int asc, int nulls_fi
             *n_out = need_total;
         }
     }
-    hipFree(buf);
     return rc;
 }
 
@@ -505,19 +505,18 @@ int sort_multi_limit_run(hipStream_t s, const MKeyDesc& K, u64 rows, u64 limit, 
     if (blocks < 1) blocks = 1;
     // scratch: hist[256] u32 | counter | maxlen, and/or u64 x 2 | cand u32 x SORT_CAP; prefix and
     // candidate words allocated once W is known
-    char* buf = nullptr;
+    Buf<char> buf;
     const size_t head = 1024 + 16 + 32 + (size_t)SORT_CAP * 4;
-    if (hipMalloc((void**)&buf, head) != hipSuccess) {
+    if (buf.ensure(head) != DBG_OK) {
         err = "sort limit: device allocation failed";
         return DBG_ERR_OOM;
     }
-    u32* hist = (u32*)buf;
+    u32* hist = (u32*)buf.get();
     u32* counter = (u32*)(buf + 1024);
     u64* maxlen = (u64*)(buf + 1024 + 16);
     u64* andor = maxlen + 2;
     u32* cand = (u32*)(buf + 1024 + 16 + 32);
-    u64* pref = nullptr;
-    u64* words = nullptr;
+    Buf<u64> pref, words;
     int rc = DBG_OK;
     u32 W = 0;
     {
@@ -531,8 +530,7 @@ int sort_multi_limit_run(hipStream_t s, const MKeyDesc& K, u64 rows, u64 limit, 
         }
         W = (u32)((ml + 7) / 8);
         const u64 n_max = rows <= SORT_CAP ? rows : need_total;
-        if (rc == DBG_OK && (hipMalloc((void**)&pref, (size_t)(W + 1) * 8) != hipSuccess ||
-                             hipMalloc((void**)&words, (size_t)n_max * (W ? W : 1) * 8) != hipSuccess)) {
+        if (rc == DBG_OK && (pref.ensure(W + 1) != DBG_OK || words.ensure(n_max * (W ? W : 1)) != DBG_OK)) {
             err = "sort limit: device allocation failed";
             rc = DBG_ERR_OOM;
         }
@@ -640,20 +638,20 @@ int sort_multi_limit_run(hipStream_t s, const MKeyDesc& K, u64 rows, u64 limit, 
         } else {
             if (W) {
                 u64 gb = ((u64)got * W + SBLOCK - 1) / SBLOCK;
-                hipLaunchKernelGGL(mkey_gather_kernel, dim3((u32)(gb > 4096 ? 4096 : gb)), dim3(SBLOCK), 0, s, K, cand, got, W, words);
+                hipLaunchKernelGGL(mkey_gather_kernel, dim3((u32)(gb > 4096 ? 4096 : gb)), dim3(SBLOCK), 0, s, K, cand, got, W, words.get());
             }
             // the n_cand candidates sorted; the first need_total written
             u32* sorted = idx_out;
-            u32* tmp = nullptr;
+            Buf<u32> tmp;
             if (n_cand > need_total) {
-                if (hipMalloc((void**)&tmp, n_cand * 4) != hipSuccess) {
+                if (tmp.ensure(n_cand) != DBG_OK) {
                     err = "sort limit: device allocation failed";
                     rc = DBG_ERR_OOM;
                 }
                 sorted = tmp;
             }
             if (rc == DBG_OK) {
-                hipLaunchKernelGGL(mkey_sort_kernel, dim3(1), dim3(SORT_NT), 0, s, words, cand, (u32)n_cand, W, sorted);
+                hipLaunchKernelGGL(mkey_sort_kernel, dim3(1), dim3(SORT_NT), 0, s, words.get(), cand, (u32)n_cand, W, sorted);
                 if (tmp) hipMemcpyAsync(idx_out, tmp, need_total * 4, hipMemcpyDeviceToDevice, s);
                 e = hipStreamSynchronize(s);
                 if (e != hipSuccess) {
@@ -663,11 +661,7 @@ int sort_multi_limit_run(hipStream_t s, const MKeyDesc& K, u64 rows, u64 limit, 
                     *n_out = need_total;
                 }
             }
-            if (tmp) hipFree(tmp);
         }
     }
-    if (words) hipFree(words);
-    if (pref) hipFree(pref);
-    hipFree(buf);
     return rc;
 }
