@@ -24,6 +24,10 @@ AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_AVG, AGG_AVG_SQL = range(6)
 # dbg_agg_set_strategy
 STRATEGY_AUTO, STRATEGY_TABLE, STRATEGY_PARTITIONED = range(3)
 
+# dbg_agg_insert_paths: the insert variants, in the header's order
+INSERT_PATHS = ("generic", "generic_lenpred", "fast", "fast_pred", "str1", "str1_pred", "short",
+                "pp_generic", "pp_fixed", "pp_str")
+
 # dbg_cmp
 CMP_EQ, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE = range(6)
 

@@ -262,6 +262,15 @@ class AggregateHashTable:
         check(lib().dbg_agg_get_pp_stats(self.h, C.byref(b), C.byref(s)))
         return b.value, s.value
 
+    def insert_paths(self) -> dict:
+        """Launches of each insert kernel since the handle was created, by name
+        (dbg_agg_insert_paths; abi.INSERT_PATHS): inserts into the HBM table, record merges
+        included, and the level-1 form ("pp_*") of each batch of the partitioned payload."""
+        n = len(abi.INSERT_PATHS)
+        counts = (C.c_uint64 * n)()
+        check(lib().dbg_agg_insert_paths(self.h, counts, n))
+        return dict(zip(abi.INSERT_PATHS, (int(c) for c in counts)))
+
     # ---- AggregateHashTable::add_groups (+ fused filter)
     def add_groups(self, group_columns: Sequence[ColumnLike], params: Sequence[Optional[ColumnLike]],
                    rows: Optional[int] = None, filter_program=None, on_device: Optional[bool] = None) -> None:

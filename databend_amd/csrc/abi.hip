@@ -376,7 +376,7 @@ static int flush_deferred(dbg_agg_handle* h) {
     h->def_on = false;
     {
         prof::Scope ps("agg_insert", h->stream);
-        launch_insert(h->stream, h->dspec, h->spec, h->dbatches, h->def_bid, h->def_rows, false, table_desc(h), true, &h->def_hb);
+        note_insert(h, launch_insert(h->stream, h->dspec, h->spec, h->dbatches, h->def_bid, h->def_rows, false, table_desc(h), true, &h->def_hb));
     }
     HIPCHECK(hipGetLastError());
     return DBG_OK;
@@ -611,6 +611,12 @@ static int fill_filter(dbg_agg_handle* h, const dbg_filter* f, int on_device, DC
         if (n.op == DBG_PRED_CMP_CONST || n.op == DBG_PRED_CMP_COLS || n.op == DBG_PRED_IS_NULL || n.op == DBG_PRED_IS_NOT_NULL) {
             if (n.col < 0 || n.col >= f->n_cols || (n.op == DBG_PRED_CMP_COLS && (n.col2 < 0 || n.col2 >= f->n_cols)))
                 return fail(DBG_ERR_INVALID, "predicate column index out of range");
+            if (n.op == DBG_PRED_CMP_COLS) {  // cmp_cols reads both cells as the left column's type
+                const dbg_datatype &a = f->cols[n.col].dt, &b = f->cols[n.col2].dt;
+                if (a.type != b.type) return fail(DBG_ERR_INVALID, "column comparison: the two columns differ in type");
+                if (a.type == DBG_DECIMAL128 && a.scale != b.scale)
+                    return fail(DBG_ERR_INVALID, "column comparison: the two Decimal columns differ in scale");
+            }
             depth++;
         } else if (n.op == DBG_PRED_TRUE) {
             depth++;
@@ -1046,6 +1052,7 @@ static int pp_add_batch(dbg_agg_handle* h, const BatchDesc* st, u32 bid, u64 row
     auto& K = h->ppk[kind];
     PPFast F = pp_fast_desc(S, *st, bid, kind);
     F.dig = nullptr;
+    if (kind == 0) note_insert(h, F.kind == 2 ? INS_PP_STR : (F.kind == 1 ? INS_PP_FIXED : INS_PP_GENERIC));
     const u32 rw = kind ? S.pp_rw_state : S.pp_rw_raw;
     std::vector<PPChunk> ch;
     for (u64 s = 0; s < rows; s += PP_CHUNK) ch.push_back(PPChunk{s, std::min<u64>(PP_CHUNK, rows - s), bid, 0});
@@ -1426,7 +1433,7 @@ static int add_groups_now(dbg_agg_handle* h, const dbg_column* group_cols, const
     }
     {
         prof::Scope ps("agg_insert", h->stream);
-        launch_insert(h->stream, h->dspec, S, h->dbatches, bid, rows, false, table_desc(h), true, st);
+        note_insert(h, launch_insert(h->stream, h->dspec, S, h->dbatches, bid, rows, false, table_desc(h), true, st));
     }
     HIPCHECK(hipGetLastError());
     if (!on_device) RETURN_IF(resolve_overflow(h));  // host path: synchronous like the reference processor
@@ -1836,6 +1843,12 @@ int dbg_agg_get_pp_stats(dbg_agg_handle* h, uint32_t* final_bits, uint64_t* spil
     return DBG_OK;
 }
 
+int dbg_agg_insert_paths(dbg_agg_handle* h, uint64_t* counts, int32_t n) {
+    if (!h || !counts || n < 0) return fail(DBG_ERR_INVALID, "null argument");
+    for (int32_t i = 0; i < n; ++i) counts[i] = i < INS_N_PATHS ? h->insert_paths[i] : 0;
+    return DBG_OK;
+}
+
 int dbg_agg_set_partition_keys(dbg_agg_handle* h, int n_keys) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
     if (n_keys < 0 || n_keys > h->spec.n_keys) return fail(DBG_ERR_INVALID, "partition keys: 0..n_group_cols");
@@ -2036,7 +2049,7 @@ static int fin_launch(dbg_agg_handle* h) {
         }
         h->def_on = false;
         prof::Scope ps("agg_insert", h->stream);
-        launch_insert(h->stream, h->dspec, S, h->dbatches, h->def_bid, h->def_rows, false, t, true, &h->def_hb, &ff);
+        note_insert(h, launch_insert(h->stream, h->dspec, S, h->dbatches, h->def_bid, h->def_rows, false, t, true, &h->def_hb, &ff));
     } else if (small) {
         prof::Scope ps("finalize_small", h->stream);
         launch_finalize_small(h->stream, h->dspec, h->dbatches, t, od, totals, F.zero_copy ? h->hcounters_dev : nullptr,
@@ -2431,7 +2444,7 @@ int dbg_agg_merge_fixed(dbg_agg_handle* h, const void* dev_bufs, int32_t n_bufs,
     u64 blocks = std::min<u64>(2048, (n + 4095) / 4096) + 1;
     RETURN_IF(ensure_ovf(h, n, blocks * 4096));
     prof::Scope ps("agg_merge", h->stream);
-    launch_insert(h->stream, h->dspec, S, h->dbatches, bid, n, true, table_desc(h), true);
+    note_insert(h, launch_insert(h->stream, h->dspec, S, h->dbatches, bid, n, true, table_desc(h), true));
     HIPCHECK(hipGetLastError());
     return DBG_OK;
 }
@@ -2470,7 +2483,7 @@ static int merge_record_batch(dbg_agg_handle* h, const u8* base, u64 n, const u8
     u64 blocks = std::min<u64>(2048, (n + 4095) / 4096) + 1;
     RETURN_IF(ensure_ovf(h, n, blocks * 4096));
     prof::Scope ps("agg_merge", h->stream);
-    launch_insert(h->stream, h->dspec, S, h->dbatches, bid, n, true, table_desc(h), true);
+    note_insert(h, launch_insert(h->stream, h->dspec, S, h->dbatches, bid, n, true, table_desc(h), true));
     HIPCHECK(hipGetLastError());
     return DBG_OK;
 }

@@ -164,6 +164,7 @@ struct dbg_agg_handle {
     u32 def_part_sb = 0;
     int def_part_kw = 0;
     Buf<u64> part_status;  // the direct stage's look-back words
+    u64 insert_paths[INS_N_PATHS] = {};  // launch_insert calls by the kernel they took, since create (dbg_agg_insert_paths)
     u64 table_rows = 0;  // rows / records inserted into the HBM table since the last reset
     u64 remerged = 0;    // of which records dbg_agg_compact merged back (groups, not input rows)
     int strategy = DBG_STRATEGY_AUTO;
@@ -254,6 +255,10 @@ inline const char* handle_local_reason(const Spec& S) {
         if (const char* why_ = handle_local_reason((h)->spec))                                \
             return fail(DBG_ERR_UNSUPPORTED, std::string(what) + ": " + why_);               \
     } while (0)
+
+inline void note_insert(dbg_agg_handle* h, InsertPath p) {
+    if (p >= 0 && p < INS_N_PATHS) h->insert_paths[p]++;
+}
 
 // handle helpers abi.hip defines for the other units (dev_alloc: dev_buf.hpp)
 int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtypes);

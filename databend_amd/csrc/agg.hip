@@ -3212,9 +3212,9 @@ bool insert_can_fuse(const Spec& S, const BatchDesc& hb, u64 cap) {
            (cap + 1) * S.stride_words * 8 <= fast_shmem(fast_table_bytes(S));
 }
 
-void launch_insert(hipStream_t s, const Spec* dspec, const Spec& S, const BatchDesc* batches, u32 bid, u64 rows, bool records,
-                   const TableDesc& t, bool use_lds, const BatchDesc* hb, const FusedFin* fused) {
-    if (rows == 0) return;
+InsertPath launch_insert(hipStream_t s, const Spec* dspec, const Spec& S, const BatchDesc* batches, u32 bid, u64 rows, bool records,
+                         const TableDesc& t, bool use_lds, const BatchDesc* hb, const FusedFin* fused) {
+    if (rows == 0) return INS_NONE;
     if (hb && use_lds && fast_eligible(S, *hb, records)) {
         u32 lslots = lds_slots_for(S, 16 * 1024);
         size_t shmem = fast_table_bytes(S);
@@ -3222,15 +3222,16 @@ void launch_insert(hipStream_t s, const Spec* dspec, const Spec& S, const BatchD
         int op = pred ? hb->nodes[0].cmp : 0;
         i64 c = pred ? hb->nodes[0].i64v : 0;
         int count_only = S.n_aggs == 1 && S.aggs[0].kind == DBG_AGG_COUNT && S.aggs[0].arg_type < 0 && S.aggs[0].w0 == 1;
+        const InsertPath path = pred ? INS_FAST_PRED : INS_FAST;
         switch (hb->keys[0].type) {
-            case DBG_INT8: launch_fast_t<int8_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return;
-            case DBG_UINT8: launch_fast_t<uint8_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return;
-            case DBG_INT16: launch_fast_t<int16_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return;
-            case DBG_UINT16: launch_fast_t<uint16_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return;
-            case DBG_INT32: case DBG_DATE: launch_fast_t<int32_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return;
-            case DBG_UINT32: launch_fast_t<uint32_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return;
-            case DBG_INT64: case DBG_TIMESTAMP: launch_fast_t<int64_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return;
-            case DBG_UINT64: launch_fast_t<uint64_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return;
+            case DBG_INT8: launch_fast_t<int8_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_UINT8: launch_fast_t<uint8_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_INT16: launch_fast_t<int16_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_UINT16: launch_fast_t<uint16_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_INT32: case DBG_DATE: launch_fast_t<int32_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_UINT32: launch_fast_t<uint32_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_INT64: case DBG_TIMESTAMP: launch_fast_t<int64_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_UINT64: launch_fast_t<uint64_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
         }
     }
     // one non-null String key into a large key-caching table, filtered by `key <op> ''` or not
@@ -3249,7 +3250,7 @@ void launch_insert(hipStream_t s, const Spec* dspec, const Spec& S, const BatchD
         blocks = (rows + rpb - 1) / rpb;
         if (hb->n_nodes) hipLaunchKernelGGL(agg_insert_str1_kernel<true>, dim3((u32)blocks), dim3(STR1_NT), shmem, s, dspec, batches, bid, rows, rpb, t, ls, fper, x_mode);
         else hipLaunchKernelGGL(agg_insert_str1_kernel<false>, dim3((u32)blocks), dim3(STR1_NT), shmem, s, dspec, batches, bid, rows, rpb, t, ls, fper, x_mode);
-        return;
+        return hb->n_nodes ? INS_STR1_PRED : INS_STR1;
     }
     u32 lslots = use_lds ? lds_slots_for(S, LDS_BUDGET_BYTES) : 1;
     static const int x_short = X_ENV("DBG_X_SHORT") ? atoi(X_ENV("DBG_X_SHORT")) : 1;
@@ -3313,7 +3314,7 @@ void launch_insert(hipStream_t s, const Spec* dspec, const Spec& S, const BatchD
         }
         hipLaunchKernelGGL(agg_insert_short_kernel, dim3((u32)blocks), dim3(BLOCK), shmem, s, dspec, batches, bid, rows, rpb, t, lslots,
                            x_rep ? x_rep - 1 : 0u, x_short, narrow, x_tree && S.stride_words >= S.n_words + 3 ? 1 : 0, x_tr);
-        return;
+        return INS_SHORT;
     }
     // enough workgroups to fill 256 CUs several times over, each a contiguous row range
     u64 min_rows_per_block = (u64)BLOCK * 16;
@@ -3338,6 +3339,7 @@ void launch_insert(hipStream_t s, const Spec* dspec, const Spec& S, const BatchD
         if (records) hipLaunchKernelGGL((agg_insert_kernel<false, true>), dim3((u32)blocks), dim3(BLOCK), shmem, s, dspec, batches, bid, rows, rpb, t, lslots, lenq);
         else hipLaunchKernelGGL((agg_insert_kernel<false, false>), dim3((u32)blocks), dim3(BLOCK), shmem, s, dspec, batches, bid, rows, rpb, t, lslots, lenq);
     }
+    return lenq ? INS_GENERIC_LENPRED : INS_GENERIC;
 }
 
 // Fused finalize tail: bit-pack every nullable output's validity and close the string offsets,

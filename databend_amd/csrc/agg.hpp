@@ -249,9 +249,28 @@ u64 part_direct_status_words(u64 cap, u32 sb);
 hipError_t launch_part_direct(hipStream_t s, const TableDesc& t, u32 sb, const u64* sorted, const u64* bounds, u64* status, int key_width,
                               void* out_key, u64* out_cnt, u64 cap_groups, u64* totals);
 void launch_table_init(hipStream_t s, const Spec* dspec, const Spec& hspec, u64* slots, u64 cap, u64* zero_counters = nullptr);
-void launch_insert(hipStream_t s, const Spec* dspec, const Spec& hspec, const BatchDesc* batches, u32 bid, u64 rows,
-                   bool records, const TableDesc& t, bool use_lds, const BatchDesc* host_batch = nullptr,
-                   const FusedFin* fused = nullptr);
+// the insert kernel a launch_insert call took (dbg_agg_insert_paths counts them per handle, in
+// this order); INS_NONE: no rows, nothing launched
+enum InsertPath {
+    INS_NONE = -1,
+    INS_GENERIC = 0,      // agg_insert_kernel
+    INS_GENERIC_LENPRED,  // agg_insert_kernel with the `string <op> ''` queue
+    INS_FAST,             // agg_insert_fast_kernel, no predicate
+    INS_FAST_PRED,        // agg_insert_fast_kernel, `key <op> const` folded into a range
+    INS_STR1,             // agg_insert_str1_kernel<false>
+    INS_STR1_PRED,        // agg_insert_str1_kernel<true>
+    INS_SHORT,            // agg_insert_short_kernel
+    // level 1 of the partitioned payload (pp_add_batch counts these; launch_insert never returns them)
+    INS_PP_GENERIC,       // pp_count / pp_scatter_direct_kernel: eval_pred
+    INS_PP_FIXED,         // pp_l1_fixed_kernel: fixed-width keys and arguments, pp_fast_pred
+    INS_PP_STR,           // the String-key form: cmp3_bytes against the constant
+    INS_N_PATHS
+};
+static_assert(INS_N_PATHS == DBG_INSERT_N_PATHS && INS_SHORT == DBG_INSERT_SHORT && INS_PP_STR == DBG_INSERT_PP_STR,
+              "InsertPath follows the header's order");
+InsertPath launch_insert(hipStream_t s, const Spec* dspec, const Spec& hspec, const BatchDesc* batches, u32 bid, u64 rows,
+                         bool records, const TableDesc& t, bool use_lds, const BatchDesc* host_batch = nullptr,
+                         const FusedFin* fused = nullptr);
 void launch_retry(hipStream_t s, const Spec* dspec, const Spec& hspec, const BatchDesc* batches, const TableDesc& t,
                   u64 n_rows, u64 n_recs, const u64* rows_list, const u64* recs_list);
 void launch_rehash(hipStream_t s, const Spec* dspec, const Spec& hspec, const BatchDesc* batches, const u64* old_slots,

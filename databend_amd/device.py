@@ -70,7 +70,7 @@ class DeviceColumn:
         elif t in (abi.DECIMAL128, abi.DECIMAL256):
             data = raw[:n * self.dtype.width]
         else:
-            data = raw.view(self.dtype.np_dtype)[:n]
+            data = raw[:n * self.dtype.width].view(self.dtype.np_dtype)  # an empty column's buffer holds one spare byte
         val = None
         if self.validity is not None and self.dtype.nullable:
             val = np.unpackbits(self.validity.cpu().numpy(), bitorder="little")[:n].astype(bool)

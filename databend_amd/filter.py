@@ -16,6 +16,7 @@ from typing import List, Sequence
 
 from . import abi
 from .column import Column
+from .ffi import DbgError
 
 _CMP = {"=": abi.CMP_EQ, "==": abi.CMP_EQ, "<>": abi.CMP_NE, "!=": abi.CMP_NE, "<": abi.CMP_LT,
         "<=": abi.CMP_LE, ">": abi.CMP_GT, ">=": abi.CMP_GE}
@@ -119,6 +120,12 @@ class FilterProgram:
             n.col2 = d.get("col2", 0)
             if "const" in d:
                 self._set_const(n, self.cols[n.col], d["const"])
+            if n.op == abi.PRED_CMP_COLS and max(n.col, n.col2) < len(self.cols) and min(n.col, n.col2) >= 0:
+                a, b = self.cols[n.col].dt, self.cols[n.col2].dt  # the library refuses the same way (fill_filter)
+                if a.type != b.type:
+                    raise DbgError(abi.DBG_ERR_INVALID, "column comparison: the two columns differ in type")
+                if a.type == abi.DECIMAL128 and a.scale != b.scale:
+                    raise DbgError(abi.DBG_ERR_INVALID, "column comparison: the two Decimal columns differ in scale")
         self.col_arr = (abi.dbg_column * max(1, len(self.cols)))(*self.cols)
         self.struct = abi.dbg_filter(self.nodes, len(post), len(self.cols), self.col_arr)
 

@@ -60,9 +60,23 @@ def take(col: DeviceColumn, idx) -> DeviceColumn:
         out.data = out.data[: max(1, total.value)]
         return out
     out = empty(col.dtype, n, device=col.data.device)
+    if n == 0:  # an empty index tensor has no address to pass
+        return out
     check(lib().dbg_take_fixed(C.byref(col.to_abi()), idx.data_ptr(), n, out.data.data_ptr(),
                                out.validity.data_ptr() if out.validity is not None else None, None))
+    if col.dtype.type_id == abi.BOOLEAN:
+        out.data = _pack_bool_bytes(out.data, n)
     return out
+
+
+def _pack_bool_bytes(values, n: int):
+    """dbg_take_fixed gathers a Boolean column as one value byte per row; a DeviceColumn holds
+    Boolean values as an arrow bitmap (to_abi / to_host read bits, LSB first): pack them."""
+    import torch
+    padded = torch.zeros((n + 7) // 8 * 8, dtype=torch.uint8, device=values.device)
+    padded[:n] = values[:n] != 0
+    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=values.device)
+    return (padded.view(-1, 8) * weights).sum(dim=1, dtype=torch.uint8)
 
 
 def sort_multi_limit_indices(columns: Sequence[DeviceColumn], descriptions: Sequence[SortColumnDescription],

@@ -127,7 +127,8 @@ typedef enum { DBG_CMP_EQ = 0, DBG_CMP_NE, DBG_CMP_LT, DBG_CMP_LE, DBG_CMP_GT, D
 
 typedef enum {
     DBG_PRED_CMP_CONST = 0, /* column <cmp> constant (constant in the column's own domain) */
-    DBG_PRED_CMP_COLS = 1,  /* column <cmp> column2 (same type) */
+    DBG_PRED_CMP_COLS = 1,  /* column <cmp> column2 (same type, and for Decimal128 the same scale:
+                             * anything else is refused with DBG_ERR_INVALID) */
     DBG_PRED_AND = 2,       /* pops 2, pushes 1 (SQL three-valued logic) */
     DBG_PRED_OR = 3,
     DBG_PRED_NOT = 4,       /* pops 1 */
@@ -365,6 +366,31 @@ int dbg_agg_get_strategy(dbg_agg_handle* h, int* partitioned, uint64_t* extra_ro
  * neither ran).  Both are read from what the finalize already copied to the host: the call never
  * touches the device. */
 int dbg_agg_get_pp_stats(dbg_agg_handle* h, uint32_t* final_bits, uint64_t* spilled_partitions);
+/* Which insert kernel the handle's work took, cumulative since dbg_agg_create (a reset keeps
+ * the counts): counts[i] = launches of variant i, for i < n; entries past DBG_INSERT_N_PATHS are
+ * set to 0.  Every insert into the HBM table is counted under the variant it took: the batches of
+ * dbg_agg_add_groups (one held back for a fused finalize when it is launched), and also the
+ * record merges (dbg_agg_merge_records / dbg_agg_merge_fixed / dbg_agg_merge_serialized, which
+ * take the generic kernel) — so compare counts before and after the call of interest rather
+ * than against zero on a handle that also merges.  A dbg_agg_add_groups batch that goes to the
+ * partitioned payload is counted once under the level-1 form that scattered it (DBG_INSERT_PP_*), whether or not any
+ * row passed its predicate.  Host bookkeeping only: the call never touches the device. */
+enum {
+    DBG_INSERT_GENERIC = 0,         /* the general kernel: any keys, any predicate program */
+    DBG_INSERT_GENERIC_LENPRED = 1, /* the general kernel, `string <op> ''` read from the offsets */
+    DBG_INSERT_FAST = 2,            /* one non-null integer key, no predicate */
+    DBG_INSERT_FAST_PRED = 3,       /* the same with `key <op> const` folded into a range test */
+    DBG_INSERT_STR1 = 4,            /* one non-null String key, key-caching table, no predicate */
+    DBG_INSERT_STR1_PRED = 5,       /* the same with `key <op> ''` */
+    DBG_INSERT_SHORT = 6,           /* 1-2 short String keys into a small table */
+    DBG_INSERT_PP_GENERIC = 7,      /* partitioned payload, generic level 1: any predicate program */
+    DBG_INSERT_PP_FIXED = 8,        /* specialised level 1: fixed-width non-null keys and arguments,
+                                     * at most `fixed column <op> const` on a non-null column */
+    DBG_INSERT_PP_STR = 9,          /* specialised level 1: one non-null String key, COUNT(*), at
+                                     * most `key <op> string constant` on the key's own column */
+    DBG_INSERT_N_PATHS = 10
+};
+int dbg_agg_insert_paths(dbg_agg_handle* h, uint64_t* counts, int32_t n);
 
 /* ---- partial-state records: exchange / partition bucket (EAGG/payload.rs:356-391,
  *      EAGG/partitioned_payload.rs:100-143, AGG/aggregate_exchange_injector.rs:154-235) ----

@@ -1859,7 +1859,27 @@ int orc_result_type(const dbg_agg_spec* s, dbg_datatype* out) {
     }
 }
 
+// A column-against-column node compares two cells of one type (and, for Decimal128, one scale):
+// anything else is refused, as the GPU library's fill_filter does.
+static const char* cmp_cols_mismatch(const dbg_filter* f) {
+    for (int k = 0; f && k < f->n_nodes; ++k) {
+        const dbg_pred_node& n = f->nodes[k];
+        if (n.op != DBG_PRED_CMP_COLS) continue;
+        if (n.col < 0 || n.col >= f->n_cols || n.col2 < 0 || n.col2 >= f->n_cols) return "predicate column index out of range";
+        const dbg_datatype &a = f->cols[n.col].dt, &b = f->cols[n.col2].dt;
+        if (a.type != b.type) return "column comparison: the two columns differ in type";
+        if (a.type == DBG_DECIMAL128 && a.scale != b.scale) return "column comparison: the two Decimal columns differ in scale";
+    }
+    return nullptr;
+}
+#define REFUSE_CMP_COLS_MISMATCH(f)                  \
+    if (const char* why_ = cmp_cols_mismatch(f)) {   \
+        g_err = why_;                                \
+        return DBG_ERR_INVALID;                      \
+    }
+
 int orc_filter_select(const dbg_filter* f, uint64_t rows, uint32_t* sel, uint64_t* n_sel) {
+    REFUSE_CMP_COLS_MISMATCH(f);
     try {
         u64 n = 0;
         for (u64 i = 0; i < rows; ++i)
@@ -1876,6 +1896,7 @@ int orc_filter_select(const dbg_filter* f, uint64_t rows, uint32_t* sel, uint64_
 // dt.type = -1).  filter may be NULL.
 int orc_aggregate(const dbg_column* keys, int n_keys, const dbg_column* args, const dbg_agg_spec* specs, int n_aggs,
                   const dbg_filter* filter, uint64_t rows, int threads, orc_result** out) {
+    REFUSE_CMP_COLS_MISMATCH(filter);
     try {
         PipelineSpec ps;
         ps.keys.assign(keys, keys + n_keys);
@@ -1900,6 +1921,7 @@ int orc_aggregate(const dbg_column* keys, int n_keys, const dbg_column* args, co
 // The same pipeline, the final states serialized (AggregateMeta::Serialized's Binary columns).
 int orc_aggregate_serialized(const dbg_column* keys, int n_keys, const dbg_column* args, const dbg_agg_spec* specs,
                              int n_aggs, const dbg_filter* filter, uint64_t rows, int threads, orc_result** out) {
+    REFUSE_CMP_COLS_MISMATCH(filter);
     try {
         PipelineSpec ps;
         ps.keys.assign(keys, keys + n_keys);

@@ -95,6 +95,16 @@ def test_library_refuses_bad_arguments_without_gpu():
     out = abi.dbg_datatype()
     assert L.dbg_agg_result_type(C.byref(spec), C.byref(out)) == abi.DBG_ERR_UNSUPPORTED
     assert b"sum" in L.dbg_last_error()
+    counts = (C.c_uint64 * len(abi.INSERT_PATHS))()
+    assert L.dbg_agg_insert_paths(None, counts, len(counts)) == abi.DBG_ERR_INVALID
+
+
+def test_insert_path_names_follow_the_header():
+    """abi.INSERT_PATHS names the DBG_INSERT_* variants in the header's order."""
+    txt = open(HEADERS[0]).read()
+    enum = re.findall(r"DBG_INSERT_(\w+) = (\d+)", txt)
+    assert [n.lower() for n, _ in enum[:-1]] == list(abi.INSERT_PATHS) and [int(v) for _, v in enum] == list(range(len(enum)))
+    assert enum[-1] == ("N_PATHS", str(len(abi.INSERT_PATHS)))
 
 
 def test_rccl_unique_id_without_device():

@@ -29,9 +29,13 @@ def _torch():
     return torch
 
 
-def gpu_aggregate(keys, aggs, filt=None, on_device=False, capacity_hint=0, batches=1, strategy=abi.STRATEGY_AUTO, info=None):
+def gpu_aggregate(keys, aggs, filt=None, on_device=False, capacity_hint=0, batches=1, strategy=abi.STRATEGY_AUTO, info=None,
+                  share_filter_columns=False):
     """aggs: list of (name, Column|None).  filt: (pred, [Columns]) or None.  info (dict, optional)
-    receives the handle's strategy after the run."""
+    receives the handle's strategy and its insert-path counts after the run.  share_filter_columns
+    (device input only): a filter column that is the same host Column object as a key or an
+    argument is passed as that key's / argument's device column, not as a copy of its own — the
+    specialised predicate paths require the predicate to read the key's own buffer."""
     fns = [F.get(n, [], [c.dtype] if c is not None else []) for n, c in aggs]
     params = AggregatorParams([k.dtype for k in keys], fns)
     ht = AggregateHashTable(params, HashTableConfig(True, capacity_hint))
@@ -52,7 +56,10 @@ def gpu_aggregate(keys, aggs, filt=None, on_device=False, capacity_hint=0, batch
                 ks = [DeviceColumn.from_host(k) for k in ks]
                 ars = [None if c is None else DeviceColumn.from_host(c) for c in ars]
                 if fcols is not None:
-                    fcols = [DeviceColumn.from_host(c) for c in fcols]
+                    shared = {}
+                    if share_filter_columns:
+                        shared = {id(h): d for h, d in zip([c for _, c in aggs] + list(keys), ars + ks) if h is not None}
+                    fcols = [shared[id(h)] if id(h) in shared else DeviceColumn.from_host(c) for h, c in zip(filt[1], fcols)]
             if fcols is not None:
                 fp = FilterProgram(filt[0], fcols)  # keeps the (device) columns alive
             ht.add_groups(ks, ars, rows=hi - lo, filter_program=fp, on_device=on_device)
@@ -61,6 +68,7 @@ def gpu_aggregate(keys, aggs, filt=None, on_device=False, capacity_hint=0, batch
             info["partitioned"], info["extra_rounds"] = ht.strategy()
             info["specialised"] = ht.pp_specialised()
             info["pp_bits"], info["spilled"] = ht.pp_stats()
+            info["insert_paths"] = ht.insert_paths()
     finally:
         ht.close()
     na = len(aggs)
@@ -391,10 +399,14 @@ def test_fast_path_predicates(t, lo, hi):
     cases = [("=", c), ("<>", c), ("<", c), ("<=", c), (">", c), (">=", c)]
     if t.type_id in (abi.INT8, abi.INT16):
         cases += [("<>", 10**6), ("<", -10**6), (">=", -10**6)]
+    info = {}
     for op, const in cases:
-        check_parity([key], [("count", None)], filt=(cmp(0, op, const), [key]), on_device=True)
+        check_parity([key], [("count", None)], filt=(cmp(0, op, const), [key]), on_device=True, share_filter_columns=True, info=info)
+        assert info["insert_paths"]["fast_pred"] > 0, (op, const, info["insert_paths"])
     v = Column.from_numbers(col.Int64, rng.integers(0, 100, n))
-    check_parity([key], [("count", None), ("sum", v), ("min", v)], filt=(cmp(0, "<>", c), [key]), on_device=True)
+    check_parity([key], [("count", None), ("sum", v), ("min", v)], filt=(cmp(0, "<>", c), [key]), on_device=True,
+                 share_filter_columns=True, info=info)
+    assert info["insert_paths"]["fast_pred"] > 0, info["insert_paths"]
 
 
 # (5, 20M): > 2048 x 4096 rows, so each workgroup of the queued filtered insert runs past the
