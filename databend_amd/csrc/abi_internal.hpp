@@ -1,6 +1,10 @@
 // abi_internal.hpp — what the C-ABI translation units share: the handle (one AggregateHashTable in
-// HBM), its finalize state, and the error / HIP-check helpers.  abi.hip implements the handle's
-// entry points, exchange.hip the multi-GPU exchange over RCCL.
+// HBM), its finalize state, the error / HIP-check helpers, and the functions that cross units
+// (declared at the end, by the unit that defines them; all hidden from the library's interface).
+// The units: abi.hip the handle itself (error slot, table, batches, inserts), abi_spec.hip specs and
+// layouts, abi_pp.hip the partitioned payload's host side, abi_finalize.hip both finalize families,
+// abi_records.hip records / partition / merge / compact, abi_ops.hip the handle-free entry points,
+// prof.hip the event profiler, exchange.hip the multi-GPU exchange over RCCL.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +25,7 @@
 
 #include "filter.hpp"
 #include "sort.hpp"
+#include "prof.hpp"
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -38,6 +43,13 @@ int fail(int code, const std::string& msg);
     do {              \
         int _r = (rc); \
         if (_r != DBG_OK) return _r; \
+    } while (0)
+
+// Entry points outside the hash aggregate (filter predicates, take, sort, legacy hash methods)
+// carry values as at most two words: a Decimal256 column is refused, never read with a narrower width.
+#define REFUSE_DECIMAL256(t, what)                                                                           \
+    do {                                                                                                     \
+        if ((t) == DBG_DECIMAL256) return fail(DBG_ERR_UNSUPPORTED, std::string(what) + ": Decimal256 columns are not supported"); \
     } while (0)
 
 // ------------------------------------------------------------------------------------------
@@ -260,7 +272,70 @@ inline void note_insert(dbg_agg_handle* h, InsertPath p) {
     if (p >= 0 && p < INS_N_PATHS) h->insert_paths[p]++;
 }
 
-// handle helpers abi.hip defines for the other units (dev_alloc: dev_buf.hpp)
-int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtypes);
-// (defined inside abi.hip's extern "C" block; hidden: not part of the library's interface)
+// ------------------------------------------------------------------------------------------
+// what crosses units (dev_alloc: dev_buf.hpp), by the unit that defines it
+// ------------------------------------------------------------------------------------------
+int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtypes);  // abi_spec.hip
+// Everything a caller queued (staged host rows, a held-back insert) reaches the table.  abi.hip
 extern "C" __attribute__((visibility("hidden"))) int flush_pending(dbg_agg_handle* h);
+
+#pragma GCC visibility push(hidden)
+inline bool valid_type(int t) { return t >= DBG_INT8 && t <= DBG_DECIMAL256; }
+inline u64 pow2_at_least(u64 x) {
+    u64 p = 1;
+    while (p < x) p <<= 1;
+    return p;
+}
+// worst-case overflow pushes of an insert launch over n rows: every LDS slot of every workgroup
+inline u64 ovf_blocks(u64 n) { return std::min<u64>(2048, (n + 4095) / 4096) + 1; }
+// A kernel left the table as dbg_agg_reset does (re-initialised, or never written).
+inline void mark_recycled(dbg_agg_handle* h) {
+    h->clean = true;
+    h->finalized = false;
+    h->n_batches = h->n_cached;
+    h->pending_rows = h->pending_recs = 0;
+}
+// Where the device copy of a caller's host bytes goes: the stream that fills it and the list that
+// keeps it alive ({h->stream, h->owned} for a handle).
+struct Owner {
+    hipStream_t stream;
+    std::vector<DevBuf>& owned;
+};
+
+// ---- abi.hip ----
+// CNT_ERR bits -> return code and last-error message; `mask`: the bits this caller tests
+int err_bits_fail(u64 err, u64 mask);
+int own_alloc(Owner o, size_t bytes);  // o.owned.back(): `bytes` of device memory
+DCol dcol_view(const dbg_column& c);   // a caller's device-resident column as the kernels read it
+int to_dcol(Owner o, const dbg_column& c, const dbg_datatype& want, bool check_type, int on_device, DCol& d);
+int fill_filter(Owner o, const dbg_filter* f, int on_device, DCol* cols, int* ncols, DNode* nodes, int* nnodes);
+TableDesc table_desc(dbg_agg_handle* h);
+int flush_deferred(dbg_agg_handle* h);
+int part_flush(dbg_agg_handle* h);
+int stage_flush(dbg_agg_handle* h);
+int grow_table(dbg_agg_handle* h, u64 new_cap);
+int resolve_overflow(dbg_agg_handle* h);
+int ensure_ovf(dbg_agg_handle* h, u64 add_rows, u64 add_recs);
+int new_batch(dbg_agg_handle* h, BatchDesc** staging, u32* bid);
+int upload_batch(dbg_agg_handle* h, BatchDesc* st, u32 bid);
+int submit_batch(dbg_agg_handle* h, BatchDesc** pst, u32* pbid, bool cacheable);
+// ---- abi_spec.hip ----
+u32 ser_stride_of(const DAgg& A);
+// ---- abi_pp.hip ----
+int pp_maybe_switch(dbg_agg_handle* h, u32 bid, u64 rows);
+int pp_add_batch(dbg_agg_handle* h, const BatchDesc* st, u32 bid, u64 rows, int kind);
+int pp_finalize(dbg_agg_handle* h, uint64_t* n_groups, uint64_t* string_bytes);
+int pp_fin_launch(dbg_agg_handle* h, const OutDesc& od);
+int pp_fin_complete(dbg_agg_handle* h, uint64_t* n_groups, uint64_t* string_bytes);
+// ---- abi_finalize.hip ----
+// The groups of a finalize are known: h->n_groups / h->string_bytes from the totals (str_tot[c]:
+// bytes of String key column c), the caller's outputs filled where given.  Returns whether the
+// groups or a String column exceed `caps` (the buffers of a finalize_into; nullptr: none to check).
+bool groups_known(dbg_agg_handle* h, u64 groups, const u64* str_tot, const FinState* caps, uint64_t* n_groups,
+                  uint64_t* string_bytes);
+// ---- abi_ops.hip ----
+int legacy_method(const dbg_datatype* types, int n, int* kind, uint32_t* key_bytes);
+// The FixedKeys packing (build_keys_vec) by position j in the key: the column there, its value's
+// byte offset, and its null byte's offset (-1: not nullable).
+void legacy_fixed_order(const dbg_datatype* types, int n, int* order, u32* off, int32_t* null_off);
+#pragma GCC visibility pop

@@ -117,7 +117,7 @@ def exchange_partial(partial, final, device) -> dict:
 
 
 def payload_owned(d: int, n: int, parts: int = 256):
-    """Level-1 partitions of rank d: p with p * n // parts == d (dbg_agg_payload_*, abi.hip)."""
+    """Level-1 partitions of rank d: p with p * n // parts == d (dbg_agg_payload_*, exchange.hip)."""
     return (d * parts + n - 1) // n, ((d + 1) * parts + n - 1) // n
 
 

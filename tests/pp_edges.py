@@ -6,7 +6,7 @@ A record's final partition is the top `pp_bits` bits of its group hash (pp_mix i
 The plan never uses fewer than MIN_BITS = PP_L1_BITS + 1 bits, so keys whose hashes differ in
 their top MIN_BITS bits never share a final partition; with a specialised kernel it never uses
 more than MAX_BITS = PP_L1_BITS + 10, so keys whose hashes agree in their top MAX_BITS bits always
-do (abi.hip pp_prepare).  The builders below place keys by those two facts; the tests recompute
+do (abi_pp.hip pp_prepare).  The builders below place keys by those two facts; the tests recompute
 every record's partition from the bits the finalize reports and check that the placement held.
 
 exact_reference() is plain Python-integer arithmetic per group, independent of the oracle and
@@ -22,8 +22,8 @@ from databend_amd import column as col
 from databend_amd.column import Column
 from oracle import oracle
 
-MIN_BITS = 9    # PP_L1_BITS + 1 (agg.hpp PP_L1_BITS = 8; abi.hip pp_prepare: B and b2 start there)
-MAX_BITS = 18   # PP_L1_BITS + 10 (abi.hip pp_prepare: the specialised plan's b2 stops there)
+MIN_BITS = 9    # PP_L1_BITS + 1 (agg.hpp PP_L1_BITS = 8; abi_pp.hip pp_prepare: B and b2 start there)
+MAX_BITS = 18   # PP_L1_BITS + 10 (abi_pp.hip pp_prepare: the specialised plan's b2 stops there)
 
 # Records of one final partition the kernels aggregate themselves; one more and the partition goes
 # to the generic kernel (`n > SNT * RPT`).  Written out on purpose: a retune of these constants
