@@ -18,6 +18,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from databend_amd import abi
 from databend_amd import column as col
 from databend_amd.column import Column
 from oracle import oracle
@@ -87,6 +88,18 @@ def result_dtype(name: str, arg: Optional[Column]):
     """AggregateFunction::return_type of the factory-built function (or_null wraps all but count)."""
     if name == "count":
         return col.UInt64
+    if name not in ("sum", "avg", "sql_avg", "min", "max"):
+        raise ValueError(name)
+    t = arg.dtype
+    if t.type_id == abi.DECIMAL128 and name not in ("min", "max"):
+        # SUM: Decimal(38, s) (FUN/aggregate_sum.rs:203-222); AVG: Decimal(38, max(s, 4))
+        # (FUN/aggregate_avg.rs:235-262); the SQL rewrite's divide: scale max(s, min(s + 6, 12))
+        # (EXP/types/decimal.rs:1015-1018)
+        s = t.scale
+        scale = {"sum": s, "avg": max(s, 4), "sql_avg": max(s, min(s + 6, 12))}[name]
+        return col.Decimal128(38, scale).wrap_nullable()
+    if t.type_id in (abi.FLOAT32, abi.FLOAT64) and name not in ("min", "max"):
+        return col.Float64.wrap_nullable()  # NumberSumState<f64> / NumberAvgState<_, f64>
     if name == "sum":
         return (col.Int64 if is_signed(arg.dtype) else col.UInt64).wrap_nullable()
     if name in ("avg", "sql_avg"):

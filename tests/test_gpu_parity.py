@@ -30,15 +30,16 @@ def _torch():
 
 
 def gpu_aggregate(keys, aggs, filt=None, on_device=False, capacity_hint=0, batches=1, strategy=abi.STRATEGY_AUTO, info=None,
-                  share_filter_columns=False):
+                  share_filter_columns=False, lds=True):
     """aggs: list of (name, Column|None).  filt: (pred, [Columns]) or None.  info (dict, optional)
     receives the handle's strategy and its insert-path counts after the run.  share_filter_columns
     (device input only): a filter column that is the same host Column object as a key or an
     argument is passed as that key's / argument's device column, not as a copy of its own — the
-    specialised predicate paths require the predicate to read the key's own buffer."""
+    specialised predicate paths require the predicate to read the key's own buffer.  lds=False:
+    HashTableConfig(False), every insert goes straight to the HBM table."""
     fns = [F.get(n, [], [c.dtype] if c is not None else []) for n, c in aggs]
     params = AggregatorParams([k.dtype for k in keys], fns)
-    ht = AggregateHashTable(params, HashTableConfig(True, capacity_hint))
+    ht = AggregateHashTable(params, HashTableConfig(lds, capacity_hint))
     ht.set_strategy(strategy)
     try:
         n = len(keys[0])

@@ -37,13 +37,20 @@ def _functions(aggs):
     return [F.get(n, [], [c.dtype] if c is not None else []) for n, c in aggs]
 
 
-def fused_aggregate(keys, aggs, on_device=True, batches=1, info=None):
-    """gpu_aggregate's twin on the fused finalize (dbg_agg_finalize_into, device output columns)."""
+def fused_aggregate(keys, aggs, on_device=True, batches=1, info=None, strategy=PP, capacity_hint=0, recycle=False):
+    """gpu_aggregate's twin on the fused finalize (dbg_agg_finalize_into, device output columns).
+    recycle: dbg_agg_set_recycle, under which an on-device fast insert the table can fuse is held
+    back and launched together with the finalize; info then also receives "paths_before" (the
+    insert counts before the finalize), "finalize_scopes" (the profiler scopes the finalize call
+    opened) and "groups_after" (what a second finalize finds in the recycled table)."""
+    from databend_amd import ffi
     from databend_amd.device import DeviceColumn, empty
     from databend_amd.workloads import _dev_to_host
     fns = _functions(aggs)
-    ht = AggregateHashTable(AggregatorParams([k.dtype for k in keys], fns), HashTableConfig(True))
-    ht.set_strategy(PP)
+    ht = AggregateHashTable(AggregatorParams([k.dtype for k in keys], fns), HashTableConfig(True, capacity_hint))
+    ht.set_strategy(strategy)
+    if recycle:
+        check(lib().dbg_agg_set_recycle(ht.h, 1))
     try:
         n = len(keys[0])
         bounds = np.linspace(0, n, batches + 1).astype(int)
@@ -68,12 +75,28 @@ def fused_aggregate(keys, aggs, on_device=True, batches=1, info=None):
         groups = C.c_uint64()
         sb = (C.c_uint64 * len(keys))()
         scap = (C.c_uint64 * len(keys))()
-        check(lib().dbg_agg_finalize_into(ht.h, oa, ok, n, scap, C.byref(groups), sb))
+        watch = info is not None and recycle
+        if watch:
+            info["paths_before"] = ht.insert_paths()
+            ffi.prof_reset()
+            ffi.prof_enable(True)
+        try:
+            check(lib().dbg_agg_finalize_into(ht.h, oa, ok, n, scap, C.byref(groups), sb))
+        finally:
+            if watch:
+                ffi.prof_enable(False)
+                info["finalize_scopes"] = set(ffi.prof_read())
         if info is not None:
             info["partitioned"], info["extra_rounds"] = ht.strategy()
             info["specialised"] = ht.pp_specialised()
             info["pp_bits"], info["spilled"] = ht.pp_stats()
-        return [_dev_to_host(c, groups.value) for c in out_k], [_dev_to_host(c, groups.value) for c in out_a]
+            info["insert_paths"] = ht.insert_paths()
+        result = [_dev_to_host(c, groups.value) for c in out_k], [_dev_to_host(c, groups.value) for c in out_a]
+        if watch:
+            after = C.c_uint64()
+            check(lib().dbg_agg_finalize_into(ht.h, oa, ok, n, scap, C.byref(after), sb))
+            info["groups_after"] = after.value
+        return result
     finally:
         ht.close()
 

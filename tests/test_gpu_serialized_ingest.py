@@ -91,7 +91,7 @@ def _oracle_partial_serialized(keys, aggs, lo, hi):
     return DataBlock(oa + ok)
 
 
-def _gpu_final(keys_types, aggs, blocks, on_device=False):
+def _gpu_final(keys_types, aggs, blocks, on_device=False, info=None):
     fns = [F.get(fn, [], [c.dtype] if c is not None else []) for fn, c in aggs]
     params = AggregatorParams(keys_types, fns)
     ht = AggregateHashTable(params, HashTableConfig(False))
@@ -104,6 +104,8 @@ def _gpu_final(keys_types, aggs, blocks, on_device=False):
                 cols = [DeviceColumn.from_host(c) for c in cols]
             ht.merge_serialized(cols[:na], cols[na:], rows=b.num_rows(), on_device=on_device)
         out = ht.merge_result()
+        if info is not None:
+            info["insert_paths"] = ht.insert_paths()
     finally:
         ht.close()
     return out.columns[na:], out.columns[:na]
