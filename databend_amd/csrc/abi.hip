@@ -555,7 +555,10 @@ int dbg_agg_create(const dbg_agg_params* params, dbg_agg_handle** out) {
     // parking rows for every workgroup of an insert launch (launch_insert caps its grid here)
     h->scr_blocks = DBG_INSERT_MAX_BLOCKS;
     if ((rc = h->scratch.ensure(scr_words(h->scr_blocks, (u32)h->spec.stride_words))) != DBG_OK) return cleanup(rc);
-    if (hipMemset(h->scratch, 0, (size_t)h->scr_blocks * 16) != hipSuccess) return cleanup(fail(DBG_ERR_DEVICE, "memset"));
+    // all of it: tickets and counts start at zero, and a row word that was never written must not
+    // look like a tagged entry (fused_chain_tagged)
+    if (hipMemset(h->scratch, 0, scr_words(h->scr_blocks, (u32)h->spec.stride_words) * 8) != hipSuccess)
+        return cleanup(fail(DBG_ERR_DEVICE, "memset"));
 
     // the (empty) batch table
     BatchDesc* st;

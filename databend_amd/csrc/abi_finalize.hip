@@ -223,6 +223,14 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
     return DBG_OK;
 }
 
+// The next finalize's sequence number.  Its low bits tag the parked words of the tagged fused
+// chain (agg.hip), where tag 0 belongs to no launch (a cleared word never validates): multiples of
+// the tag period are skipped.
+static u64 next_fin_seq(dbg_agg_handle* h) {
+    if ((++h->fin_seq & (FIN_SEQ_TAG_PERIOD - 1)) == 0) ++h->fin_seq;
+    return h->fin_seq;
+}
+
 // Fused finalize, split into launch and completion so a caller can overlap the device work with
 // other launches (dbg_agg_finalize_into_async / dbg_agg_finalize_wait).
 static int fin_launch(dbg_agg_handle* h) {
@@ -277,13 +285,13 @@ static int fin_launch(dbg_agg_handle* h) {
     }
     if (h->pp) {
         F.zero_copy = false;
-        F.seq = ++h->fin_seq;
+        F.seq = next_fin_seq(h);
         RETURN_IF(pp_fin_launch(h, od));
         F.active = true;
         return DBG_OK;
     }
     F.zero_copy = small && !direct && h->hcounters_dev != nullptr;
-    F.seq = ++h->fin_seq;
+    F.seq = next_fin_seq(h);
     if (direct) {
         prof::Scope ps("part_direct", h->stream);
         TableDesc td{};
@@ -302,9 +310,17 @@ static int fin_launch(dbg_agg_handle* h) {
         ff.recycle = h->recycle;
         ff.on = 1;
         ff.table_empty = h->def_clean ? 1 : 0;
+        ff.chain_tagged = 0;  // launch_fast_t decides, from its grid
         ff.trace = nullptr;
         ff.dense = nullptr;
         ff.dense_n = 0;
+        // The tagged chain accepts a parked word by its tag alone: when the tags have wrapped since
+        // the scratch was last cleared, clear it again (behind every earlier launch of the handle),
+        // so that no word of an earlier period can carry a current tag.
+        if ((F.seq / FIN_SEQ_TAG_PERIOD) != h->scr_period) {
+            HIPCHECK(hipMemsetAsync(h->scratch, 0, scr_words(h->scr_blocks, (u32)S.stride_words) * 8, h->stream));
+            h->scr_period = F.seq / FIN_SEQ_TAG_PERIOD;
+        }
         RETURN_IF(exp_fused_fin(h, F, ff));
         h->def_on = false;
         prof::Scope ps("agg_insert", h->stream);

@@ -162,7 +162,12 @@ struct dbg_agg_handle {
     // initialised): table_desc() runs it before any kernel touches the table, except a
     // partitioned insert, whose slice kernel starts every slice EMPTY and writes the whole table
     bool init_pending = false;
-    u64 fin_seq = 0;              // sequence number the finalize kernel posts to host_mirror
+    // sequence number the finalize kernel posts to host_mirror and the tagged fused chain tags its
+    // parked words with (fin_launch skips the values whose low FIN_SEQ_TAG_PERIOD bits are 0).  It
+    // starts just below the wrap of the chain's wider tag, so every handle crosses both tag wraps
+    // within its first 32 finalizes instead of after a million.
+    u64 fin_seq = (1ULL << 24) - 32;
+    u64 scr_period = ((1ULL << 24) - 32) / FIN_SEQ_TAG_PERIOD;  // fin_seq's tag period when the scratch was last cleared
     bool uploads_pending = false; // descriptor uploads from pinned staging since the last sync
     // radix-partitioned insert (part.hip): sorted mixed keys, slice bounds, rocPRIM scratch
     Buf<u64> part_sorted, part_bounds;

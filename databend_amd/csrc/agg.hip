@@ -2457,32 +2457,82 @@ __device__ __forceinline__ void fused_chain(const Spec& S, const BatchDesc* batc
 // The fused chain for COUNT(*) over a key of <= 16 bits (ClickBench Q8's Int16 AdvEngineID), with
 // self-validating parked rows so that every hand-off costs one round trip instead of three.  The
 // chain above parks a table, drains the stores, takes a ticket, and the last arrival then loads
-// the rows: store drain + ticket + loads on the critical path at both levels.  Here a workgroup
-// takes its ticket FIRST and parks only if it is not the last: the last arrival merges its own
-// table in place (no park, no reload) and loads the others' rows while they may still be landing.
+// the rows: store drain + ticket + loads on the critical path at both levels.  Here all three are
+// in flight together: a workgroup issues its ticket, parks its table without draining the stores,
+// and loads its siblings' rows while the ticket is still outstanding.  A workgroup that the
+// ticket says is not the last drops what it loaded and returns (it never waits on another
+// workgroup); the last arrival already holds the rows that had landed, polls again only the
+// items that had not, and merges them into its own LDS table in place (its own parked row is
+// read by nobody).  The ticket elects the merger and carries the HBM claims; it vouches for no
+// data, so nothing has to land before it.
 // A parked entry is one word, [key 16 b | count 24 b (level 2: 28 b) | tag 24 b (level 2: 20 b)],
-// the tag the launch's sequence number, so an entry is accepted only once this launch's word is
-// visible; the row's entry count is posted as [seq 44 b | entries 20 b] after the entries.  A
-// reader spins (bounded) on an item until both are current — no acquire / release pair, no
-// second round trip.  (A workgroup covers < 2^24 rows, a group of 16 < 2^28: the host launches
-// at most 256 workgroups over < 2^32 rows, and a grid below 256 covers <= 32768 rows each.)
+// the tag the low bits of the launch's sequence number, written by one sc1 store; the row's
+// entry count is posted as [seq 44 b | entries 20 b].  Item k of a row is an entry only if the
+// count word carries this launch's full sequence number and k is below its count, and it is
+// accepted only once its own tag is this launch's: a reader spins (bounded) on an item until
+// both hold — no acquire / release pair, no second round trip.
+// A stale word never validates: the host keeps the low TAG2_BITS of the sequence number away
+// from 0 and clears the whole scratch on the handle's stream whenever they wrap (fin_launch), and
+// clears it when the handle is created, so every word in the rows is zero (tag 0: never a
+// launch's), a word of the generic chain or the parked flush on this handle (a key of <= 16 bits
+// or a row count below 2^40: tag 0 again), or a tagged word of a launch since the last clear,
+// whose tag differs from this launch's.
+// A count never carries into the tag: the host takes this chain only when a workgroup's share of
+// the rows stays below 2^CNT1_BITS (launch_fast_t, from the grid, NT and FAST_UNROLL: with 256
+// workgroups that is rows < 2^32 - 2^22); a group of SCR_GROUP then stays below 2^CNT2_BITS.
 #ifndef CHAIN_TAGGED
 #define CHAIN_TAGGED 1  // 0: the generic chain for these launches too (A/B builds: make EXP=1 EXTRA=-DCHAIN_TAGGED=0)
 #endif
 constexpr bool kChainTagged = CHAIN_TAGGED != 0;
 #define TAG1_BITS 24
 #define TAG2_BITS 20
+#define CNT1_BITS (64 - 16 - TAG1_BITS)  // count bits of a level-1 entry
+#define CNT2_BITS (64 - 16 - TAG2_BITS)
+static_assert(FIN_SEQ_TAG_PERIOD == (1ULL << TAG2_BITS), "the host clears the scratch when the narrower tag wraps");
+static_assert(TAG2_BITS <= TAG1_BITS, "the host keeps the low TAG2_BITS of the sequence number non-zero: both tags then are");
+static_assert(((u64)SCR_GROUP << CNT1_BITS) <= (1ULL << CNT2_BITS), "a group's count fits a level-2 entry");
+static_assert(SCR_GROUP * SCR_ENTRIES <= FIN_NT, "one parked item per thread at level 1");
+#define CHAIN_TAGGED_MAX_BLOCKS (SCR_GROUP * (FIN_NT / SCR_ENTRIES))  // one group-row item per thread at level 2
 __device__ __forceinline__ u64 chain_pack(u64 key, u64 cnt, u64 seq, int level) {
     const int tb = level == 1 ? TAG1_BITS : TAG2_BITS;
     return key | (cnt << 16) | ((seq & ((1ULL << tb) - 1)) << (64 - tb));
+}
+
+// The count-only finalize straight from the last leader's LDS table (every group of the launch
+// merged into it, `total` of its lds_slots slots claimed), for a launch after which nothing
+// outlives the finalize: the HBM table was empty and stays untouched, the counters are known, the
+// table recycles.  No prefix scan: the order of result rows is free, so each entry takes its row
+// from an LDS counter (`next`, zero on entry).  Host word and counters as finalize_count_only's
+// known / recycled / compact case.
+template <typename T, int OWN>
+__device__ __forceinline__ void finalize_count_lds(const TableDesc& t, const u64* lds, u32 lds_slots, u32 sw, u32 nt, u32* next,
+                                                   u32 total, const FusedFin& ff) {
+    const OutDesc& out = ff.out;
+#pragma unroll
+    for (int j = 0; j < OWN; ++j) {
+        const u32 s = threadIdx.x + (u32)j * nt;
+        if (s >= lds_slots) continue;
+        const u64 e = lds[(u64)s * sw];
+        if (e == SLOT_EMPTY) continue;
+        const u32 p = atomicAdd(next, 1u);
+        if (p >= out.cap_groups) continue;  // (total <= cap_groups: the caller's condition)
+        ((T*)out.key_data[0])[p] = (T)e;
+        ((u64*)out.agg_data[0])[p] = lds[(u64)s * sw + 1];
+    }
+    if (threadIdx.x < CNT_WORDS) t.counters[threadIdx.x] = 0;  // dbg_agg_reset
+    if (threadIdx.x == 0) {
+        ff.totals[0] = total;
+        __hip_atomic_store(ff.host_mirror + MIRROR_COMPACT, (ff.seq << 25) | (1ULL << 24) | total, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 
 template <typename T>
 __device__ __forceinline__ void fused_chain_tagged(const Spec& S, const BatchDesc* batches, const BatchDesc& B, u64* lds, u32 lds_slots,
                                                    u32 sw, u32* lcount, u32 nt, const TableDesc& t, u32 my_claims, u32 my_ovf,
                                                    const FusedFin& ff) {
-    constexpr int OWN = 4;  // own slots per thread the last leader holds in registers (lds_slots <= 4 x nt, host-checked)
-    __shared__ u32 role, bad, vcl, wg_ovf;
+    constexpr int OWN = 4;  // own slots per thread the last leader finalizes (lds_slots <= 4 x nt, checked by the caller)
+    __shared__ u32 role, bad, vcl;
     __shared__ u64 hbm_claims, ovf_seen;
     const u32 lmask = lds_slots - 1;
     const u32 llimit = lds_slots - lds_slots / 4;
@@ -2494,47 +2544,76 @@ __device__ __forceinline__ void fused_chain_tagged(const Spec& S, const BatchDes
     const u32 n_groups = (gridDim.x + SCR_GROUP - 1) / SCR_GROUP;
     const u32 g = blockIdx.x / SCR_GROUP;
     const u32 gsize = min((u32)SCR_GROUP, gridDim.x - g * SCR_GROUP);
-    const u64 seq = ff.seq & ((1ULL << 44) - 1);
-    if (threadIdx.x == 0) wg_ovf = 0;
-    __syncthreads();
-    // A table too large for a row goes to the HBM table before the ticket, so its claims and
-    // possible overflow pushes ride on the ticket (uniform: lcount[0] is final).
-    auto flush_if_large = [&]() -> bool {
-        if (lcount[0] <= SCR_ENTRIES) return false;
-        flush_lds_direct<true, false, false, false>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
-        my_ovf += threadIdx.x == 0 ? 1u : 0u;
-        return true;
-    };
-    auto claims_and_ticket = [&](u64* ticket, u64 carried_claims, u64 carried_ovf) -> u64 {
+    const u64 seq = ff.seq & ((1ULL << 44) - 1);  // never 0: its low TAG2_BITS are not (host)
+    // LDS words of the hand-offs: lcount[0] the table's claimed slots (lds_find), [1] the
+    // workgroup's HBM claims not yet on a ticket, [2] parked entries, [3] possible overflow pushes
+    // not yet on a ticket; [1..3] are zero when the stream ends and after every hand-off.
+    auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };  // loads and stores in flight stay there
+    auto post_claims = [&]() {
         if (my_claims) atomicAdd(&lcount[1], my_claims);
-        if (my_ovf) atomicAdd(&wg_ovf, my_ovf);
+        if (my_ovf) atomicOr(&lcount[3], 1u);
         my_claims = my_ovf = 0;
+    };
+    // The rare hand-off of a workgroup that wrote the HBM table or must: a table too large for a
+    // row goes there (its possible overflow pushes counted), every HBM atomic of the workgroup is
+    // drained and its claims are in the table counter before the ticket carries them (both device
+    // atomics complete in order: the ticket's taker sees the claims).  Uniform; true = flushed.
+    auto settle_hbm = [&]() -> bool {
+        const bool large = lcount[0] > SCR_ENTRIES;
+        if (large) {
+            flush_lds_direct<true, false, false, false>(S, batches, B, lds, lds_slots, sw, nt, t, my_claims);
+            if (threadIdx.x == 0) atomicOr(&lcount[3], 1u);
+        }
+        post_claims();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        if (threadIdx.x == 0 && lcount[1]) {
+            atomicAdd((unsigned long long*)(t.counters + CNT_CLAIMS), (unsigned long long)lcount[1]);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        return large;
+    };
+    // One hand-off, everything in flight together: every thread loads its item of the siblings'
+    // rows (`m`, `w`; `others`: the item exists and is not this workgroup's own), thread 0 issues
+    // the ticket (arrivals, HBM claims and possible overflow pushes of the workgroups that took
+    // it, as the generic chain), every thread parks its slot's entry in `dst` (sc1, not drained);
+    // the entry count follows as soon as the workgroup knows it, and only then does thread 0 wait
+    // for the ticket.  Returns the inclusive ticket (thread 0).  Reads lcount[1], [3] before its
+    // barrier, clears [1..3] behind it.
+    // The ticket is an asm statement: a returning atomic the compiler can see is combined per wave,
+    // which consumes its result — a full round trip — right where it is issued, ahead of wave 0's
+    // loads and stores and of the barrier every other wave then waits at.  The asm's result
+    // register is written when the atomic returns; the `s_waitcnt` that names it stands before
+    // its first use.  (A memory operation the compiler does not count only makes its own waits
+    // for older operations longer, never shorter: vmcnt retires in order.)
+    auto hand_off = [&](u64* ticket, u64 carried_claims, u64 carried_ovf, bool flushed, u64* dst, u64* meta, int level,
+                        bool others, const u64* o_meta, const u64* o_ent, u64& m, u64& w) -> u64 {
+        m = w = 0;
+        if (others) {
+            m = ld_sc1(o_meta);
+            w = ld_sc1(o_ent);
+        }
+        u64 old, add = 0;  // old: thread 0 only, written by the first asm, read behind the second
+        if (threadIdx.x == 0) {
+            add = 1 + ((carried_claims + lcount[1]) << 16) + ((u64)((carried_ovf || lcount[3]) ? 1 : 0) << 40);
+            asm volatile("global_atomic_add_x2 %0, %1, %2, off sc0" : "=&v"(old) : "v"(ticket), "v"(add) : "memory");  // device scope, returns the old value
+        }
+        if (!flushed)
+            for (u32 s = threadIdx.x; s < lds_slots; s += nt) {
+                const u64* p = lds + (u64)s * sw;
+                if (p[0] == SLOT_EMPTY) continue;
+                const u32 k = atomicAdd(&lcount[2], 1u);
+                st_sc1(dst + k, chain_pack(p[0], p[1], seq, level));
+            }
+        lds_barrier();
         u64 tk = 0;
         if (threadIdx.x == 0) {
-            if (lcount[1]) {
-                atomicAdd((unsigned long long*)(t.counters + CNT_CLAIMS), (unsigned long long)lcount[1]);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            const u64 add = 1 + ((carried_claims + lcount[1]) << 16) + ((carried_ovf + wg_ovf) << 40);
-            tk = atomicAdd((unsigned long long*)ticket, (unsigned long long)add) + add;
+            st_sc1(meta, (seq << 20) | lcount[2]);
+            lcount[1] = lcount[2] = lcount[3] = 0;
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(old) : : "memory");  // the ticket is back
+            tk = old + add;
         }
         return tk;
-    };
-    // park the LDS table as packed words (sc1), then post the entry count (sc1, after the drain)
-    auto park_tagged = [&](u64* dst, u64* meta, int level) {
-        if (threadIdx.x == 0) lcount[2] = 0;
-        __syncthreads();
-        for (u32 s = threadIdx.x; s < lds_slots; s += nt) {
-            const u64* p = lds + (u64)s * sw;
-            if (p[0] == SLOT_EMPTY) continue;
-            const u32 k = atomicAdd(&lcount[2], 1u);
-            st_sc1(dst + k, chain_pack(p[0], p[1], seq, level));
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) st_sc1(meta, (seq << 20) | lcount[2]);
     };
     // an overflow record [key][count] (the host grows the table and finalizes again)
     auto push_kc = [&](u64 key, u64 c) {
@@ -2547,14 +2626,14 @@ __device__ __forceinline__ void fused_chain_tagged(const Spec& S, const BatchDes
         r[0] = key;
         r[1] = c;
     };
-    // item k of a parked row: spins until the row's count and (k < count) the entry are this
-    // launch's; false = no entry k.  A spin that does not settle raises ERR_CHAIN_SPIN.
-    auto read_item = [&](const u64* meta, const u64* row, u32 k, int level, u64& key, u64& cnt) -> bool {
+    // The item (count word m, entry word w, as loaded under the ticket) a thread holds of a
+    // sibling's row: an entry only if m is this launch's and k below its count, accepted once w
+    // carries this launch's tag; only what is not current yet is loaded again (bounded: a spin
+    // that does not settle raises ERR_CHAIN_SPIN).  false = no entry k.
+    auto take_item = [&](const u64* meta, const u64* ent, u32 k, int level, u64 m, u64 w, u64& key, u64& cnt) -> bool {
         const int tb = level == 1 ? TAG1_BITS : TAG2_BITS;
         const u64 tag = seq & ((1ULL << tb) - 1);
         for (u32 it = 0; it < (1u << 22); ++it) {
-            const u64 m = ld_sc1(meta);
-            const u64 w = ld_sc1(row + k);
             if ((m >> 20) == seq) {
                 if (k >= (m & 0xFFFFF)) return false;
                 if ((w >> (64 - tb)) == tag) {
@@ -2562,91 +2641,133 @@ __device__ __forceinline__ void fused_chain_tagged(const Spec& S, const BatchDes
                     cnt = (w << tb) >> (tb + 16);
                     return true;
                 }
+            } else {
+                m = ld_sc1(meta);
             }
+            w = ld_sc1(ent);
             __builtin_amdgcn_s_sleep(1);
         }
         atomicOr((unsigned long long*)(t.counters + CNT_ERR), (unsigned long long)ERR_CHAIN_SPIN);
         bad = 1;
+        // also onto the next ticket's overflow bit: the last leader — possibly another workgroup —
+        // must not take its counters for known and zero the error word unread
+        atomicOr(&lcount[3], 1u);
         return false;
     };
-    // 1. ticket first; a workgroup that is not its group's last parks
-    bool flushed = flush_if_large();
-    {
-        const u64 tk = claims_and_ticket(tickets + g, 0, 0);
-        if (threadIdx.x == 0) {
-            role = (tk & 0xFFFF) == gsize ? 1u : 0u;
-            hbm_claims = (tk >> 16) & 0xFFFFFF;
-            ovf_seen = tk >> 40;
-            wg_ovf = 0;
-            bad = 0;
-        }
-    }
-    __syncthreads();
-    if (!role) {
-        if (flushed) {
-            if (threadIdx.x == 0) st_sc1(counts + blockIdx.x, seq << 20);
-        } else {
-            park_tagged(rows + (u64)blockIdx.x * SCR_ENTRIES * sw, counts + blockIdx.x, 1);
-        }
-        return;
-    }
-    // 2. group leader: the members' rows merged into its own LDS table (emptied first when it went
-    //    to the HBM table above); its level-1 claims are on the ticket already
-    if (threadIdx.x == 0) {
-        tickets[g] = 0;  // all members have added
-        lcount[1] = 0;
-        if (flushed) lcount[0] = 0;
-    }
-    if (flushed) lds_table_init<false>(S, lds, lds_slots, sw, nt);
-    __syncthreads();
-    for (u32 f = threadIdx.x; f < gsize * SCR_ENTRIES; f += nt) {
-        const u64 b = (u64)g * SCR_GROUP + f / SCR_ENTRIES;
-        if (b == blockIdx.x) continue;
-        u64 key, c;
-        if (!read_item(counts + b, rows + b * SCR_ENTRIES * sw, f % SCR_ENTRIES, 1, key, c)) continue;
+    // a sibling's entry into the own LDS table; one that does not fit goes to the HBM table
+    auto merge_item = [&](u64 key, u64 c) {
         const int ls = lds_find<true>(S, batches, B.keys, 0, key, 0, lds, lmask, sw, lcount, llimit);
         if (ls >= 0) {
             at_add<AS_LDS>(asp<AS_LDS>(lds + (u64)ls * sw + 1), c);
-            continue;
+            return;
         }
         bool claimed;
         const u64 gs = g_find<true>(S, batches, B.keys, 0, key, 0, t, t.probe_limit, claimed);
         if (gs == ~0ULL) {
             push_kc(key, c);
             my_ovf++;
-            continue;
+            return;
         }
         my_claims += claimed ? 1 : 0;
         at_add<AS_GLB>(asp<AS_GLB>(t.slots + gs * t.stride_words + 1), c);
-    }
-    __syncthreads();
-    // 3. level 2: ticket first again; a leader that is not the last parks its group's table
-    flushed = flush_if_large();
+    };
+    // the own LDS table went to the HBM table: empty again before rows are merged into it
+    auto empty_own = [&]() {
+        lds_table_init<false>(S, lds, lds_slots, sw, nt);
+        if (threadIdx.x == 0) lcount[0] = 0;
+        __syncthreads();
+    };
+    const u32 item_row = threadIdx.x / SCR_ENTRIES, item_k = threadIdx.x % SCR_ENTRIES;  // the thread's item of the siblings' rows
+    // 1. level 1: ticket, park and the loads of the group's 15 other rows together.  (An add into
+    //    an HBM slot another workgroup claimed leaves no claim behind: every thread drains what it
+    //    has in flight before the barrier the ticket follows — nothing, unless it wrote HBM.)
+    post_claims();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_barrier();
+    bool flushed = false;
+    if (lcount[1] | lcount[3] | (lcount[0] > SCR_ENTRIES ? 1u : 0u)) flushed = settle_hbm();
+    const u64 b1 = (u64)g * SCR_GROUP + item_row;
+    const bool has1 = item_row < gsize && b1 != blockIdx.x;
+    const u64* meta1 = counts + b1;
+    const u64* ent1 = rows + b1 * SCR_ENTRIES * sw + item_k;
+    u64 m1, w1;
     {
-        const u64 tk = claims_and_ticket(t.counters + CNT_FIN_TICKET, hbm_claims, ovf_seen);
+        const u64 tk = hand_off(tickets + g, 0, 0, flushed, rows + (u64)blockIdx.x * SCR_ENTRIES * sw, counts + blockIdx.x, 1, has1,
+                                meta1, ent1, m1, w1);
+        if (threadIdx.x == 0) {
+            role = (tk & 0xFFFF) == gsize ? 1u : 0u;
+            hbm_claims = (tk >> 16) & 0xFFFFFF;
+            ovf_seen = tk >> 40;
+            bad = 0;
+            vcl = 0;
+        }
+    }
+    lds_barrier();
+    if (!role) return;
+    // 2. group leader: the members' rows merged into its own LDS table (emptied first when it went
+    //    to the HBM table above); its level-1 claims are on the ticket already
+    if (threadIdx.x == 0) tickets[g] = 0;  // all members have added
+    if (flushed) empty_own();
+    {
+        u64 key, c;
+        if (has1 && take_item(meta1, ent1, item_k, 1, m1, w1, key, c)) merge_item(key, c);
+    }
+    // 3. level 2: the same hand-off among the group leaders, over the group rows
+    post_claims();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_barrier();
+    flushed = false;
+    if (lcount[1] | lcount[3] | (lcount[0] > SCR_ENTRIES ? 1u : 0u)) flushed = settle_hbm();
+    const bool has2 = item_row < n_groups && item_row != g;
+    const u64* meta2 = gmeta + item_row;
+    const u64* ent2 = grows + (u64)item_row * SCR_ENTRIES * sw + item_k;
+    u64 m2, w2;
+    {
+        const u64 tk = hand_off(t.counters + CNT_FIN_TICKET, hbm_claims, ovf_seen, flushed, grows + (u64)g * SCR_ENTRIES * sw, gmeta + g,
+                                2, has2, meta2, ent2, m2, w2);
         if (threadIdx.x == 0) {
             role = (tk & 0xFFFF) == n_groups ? 2u : 0u;
             hbm_claims = (tk >> 16) & 0xFFFFFF;
             ovf_seen = tk >> 40;
         }
     }
-    __syncthreads();
+    lds_barrier();
     if (kPhaseTrace && ff.trace && threadIdx.x == 0) atomicMax((unsigned long long*)ff.trace + 3, (unsigned long long)__builtin_amdgcn_s_memrealtime());
-    if (role != 2) {
-        if (flushed) {
-            if (threadIdx.x == 0) st_sc1(gmeta + g, seq << 20);
-        } else {
-            park_tagged(grows + (u64)g * SCR_ENTRIES * sw, gmeta + g, 2);
-        }
-        return;
-    }
-    // 4. the last leader: its own table into registers, the view of the HBM table, own entries
-    //    and the other group rows merged into the view, finalize
+    if (role != 2) return;
+    // 4. the last leader: the other group rows merged into its own table, which then holds every
+    //    group of the launch that is not in the HBM table
     if (threadIdx.x == 0) {
         atomicExch((unsigned long long*)(t.counters + CNT_FIN_TICKET), 0ULL);
         atomicExch((unsigned long long*)(t.counters + CNT_TAIL), 0ULL);
-        vcl = 0;
         if (kPhaseTrace && ff.trace) ff.trace[4] = __builtin_amdgcn_s_memrealtime();
+    }
+    if (flushed) empty_own();
+    {
+        u64 key, c;
+        if (has2 && take_item(meta2, ent2, item_k, 2, m2, w2, key, c)) merge_item(key, c);
+    }
+    post_claims();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the HBM atomics of entries that did not fit
+    __syncthreads();
+    // this merge's own HBM claims and possible overflow pushes (on no ticket), the table's groups;
+    // read here: the view below overwrites lcount
+    const u32 own_groups = lcount[0], spill_claims = lcount[1], spill_ovf = lcount[3];
+    const bool ovf_any = ovf_seen != 0 || spill_ovf != 0;
+    // Nothing outlives the launch (the common case): the HBM table was empty and no workgroup
+    // touched it, no overflow, the table recycles and the result fits — finalize from the own
+    // table; no view, no second copy of the entries.
+    if (ff.table_empty && hbm_claims == 0 && spill_claims == 0 && !ovf_any && !bad && ff.recycle && ff.host_mirror &&
+        own_groups <= ff.out.cap_groups) {
+        if (kPhaseTrace && ff.trace && threadIdx.x == 0) ff.trace[5] = __builtin_amdgcn_s_memrealtime();
+        finalize_count_lds<T, OWN>(t, lds, lds_slots, sw, nt, &lcount[2], own_groups, ff);
+        if (kPhaseTrace && ff.trace && threadIdx.x == 0) ff.trace[6] = __builtin_amdgcn_s_memrealtime();
+        return;
+    }
+    // 5. otherwise the view of the HBM table (a copy, or constants when it is still empty), the own
+    //    table merged into it through registers, and the count-only finalize with its write-back
+    if (threadIdx.x == 0 && spill_claims) {
+        atomicAdd((unsigned long long*)(t.counters + CNT_CLAIMS), (unsigned long long)spill_claims);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     u64 okey[OWN], ocnt[OWN];
 #pragma unroll
@@ -2654,14 +2775,14 @@ __device__ __forceinline__ void fused_chain_tagged(const Spec& S, const BatchDes
         const u32 s = threadIdx.x + (u32)j * nt;
         okey[j] = SLOT_EMPTY;
         ocnt[j] = 0;
-        if (!flushed && s < lds_slots) {
+        if (s < lds_slots) {
             okey[j] = lds[(u64)s * sw];
             ocnt[j] = lds[(u64)s * sw + 1];
         }
     }
     __syncthreads();  // the view overwrites the table
     const u64 n = (t.cap + 1) * sw;  // host: <= the launch's dynamic LDS
-    const bool hbm_clean = ff.table_empty && hbm_claims == 0;
+    const bool hbm_clean = ff.table_empty && hbm_claims == 0 && spill_claims == 0;
     if (hbm_clean)  // COUNT(*) slots start [EMPTY][0]: no load of the Spec's initial slot
         for (u64 i = threadIdx.x; i < n; i += nt) lds[i] = (i % sw) == 0 ? SLOT_EMPTY : 0ULL;
     else
@@ -2680,15 +2801,9 @@ __device__ __forceinline__ void fused_chain_tagged(const Spec& S, const BatchDes
 #pragma unroll
     for (int j = 0; j < OWN; ++j)
         if (okey[j] != SLOT_EMPTY) to_view(okey[j], ocnt[j]);
-    for (u32 f = threadIdx.x; f < n_groups * SCR_ENTRIES; f += nt) {
-        const u64 gg = f / SCR_ENTRIES;
-        if (gg == g) continue;
-        u64 key, c;
-        if (read_item(gmeta + gg, grows + gg * SCR_ENTRIES * sw, f % SCR_ENTRIES, 2, key, c)) to_view(key, c);
-    }
     if (vclaims) atomicAdd(&vcl, vclaims);
     __syncthreads();
-    const bool known = ff.table_empty && ovf_seen == 0 && !bad;
+    const bool known = ff.table_empty && !ovf_any && !bad;
     if (threadIdx.x == 0 && vcl && !known) {
         atomicAdd((unsigned long long*)(t.counters + CNT_CLAIMS), (unsigned long long)vcl);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -3108,7 +3223,7 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
     }
     if (ff.on && t.scratch != nullptr && gridDim.x > 1 && gridDim.x <= t.scr_blocks) {
         if constexpr (CO && sizeof(T) <= 2) {
-            if (kChainTagged && lds_slots <= 4 * NT) {
+            if (kChainTagged && ff.chain_tagged && lds_slots <= 4 * NT) {
                 fused_chain_tagged<T>(S, batches, B, lds, lds_slots, sw, lcount, NT, t, my_claims, my_ovf, ff);
                 return;
             }
@@ -3163,6 +3278,12 @@ static void launch_fast_t(hipStream_t s, const Spec* dspec, const BatchDesc* bat
     if (blocks > max_blocks) blocks = max_blocks;
     if (blocks > DBG_INSERT_MAX_BLOCKS) blocks = DBG_INSERT_MAX_BLOCKS;
     if (blocks < 1) blocks = 1;
+    // The tagged chain packs a workgroup's count of one key into CNT1_BITS: the workgroup's share
+    // of the rows (its whole grid-stride rounds of nt vectors, one more round for the ragged end,
+    // the scalar tail) must stay below that, or a count would carry into the tag; its readers
+    // hold one item per thread, which bounds the grid.  Anything else takes the generic chain.
+    static_assert(FAST_UNROLL >= 1 && V * 1024 * FAST_UNROLL < (1ULL << CNT1_BITS), "one grid round of a workgroup fits a level-1 count");
+    ff.chain_tagged = blocks <= CHAIN_TAGGED_MAX_BLOCKS && rows / blocks + V * (u64)nt + V < (1ULL << CNT1_BITS);
     // profiling on: the kernel stamps the enclosing scope's events itself (abi.hip, prof_ext_events)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     const bool ext = prof_ext_events(&ev0, &ev1);

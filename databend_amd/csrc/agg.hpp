@@ -103,6 +103,9 @@ struct TableDesc {
 inline size_t scr_words(u32 blocks, u32 stride_words) {
     return (size_t)blocks * (2 + (size_t)SCR_ENTRIES * stride_words) + (size_t)(blocks / SCR_GROUP) * SCR_ENTRIES * stride_words;
 }
+// launches between two wraps of the tagged fused chain's narrower tag (agg.hip, TAG2_BITS): the
+// host keeps sequence numbers off its multiples and clears the scratch at each (fin_launch)
+#define FIN_SEQ_TAG_PERIOD (1ULL << 20)
 #define DBG_INSERT_MAX_BLOCKS 2048  // grid cap of every insert launch (scratch rows are sized by it)
 
 enum { CNT_CLAIMS = 0, CNT_OVF_ROWS = 1, CNT_OVF_RECS = 2, CNT_ERR = 3, CNT_FIX_FAIL = 4, CNT_FIX_TICKET = 5, CNT_FIN_TICKET = 6,
@@ -333,6 +336,7 @@ struct FusedFin {
     int recycle;
     int on;
     int table_empty;  // the HBM table held no group when the launch started (fused chain)
+    int chain_tagged;  // set by launch_fast_t: the grid and the rows admit the tagged chain's packed words
     u64* trace;  // EXPERIMENT (DBG_X_TRACE): phase timestamps of this launch, s_memrealtime ticks
     // direct-mapped hand-off for COUNT(*) over keys of <= 16 bits (fused_dense): dense_n counts then
     // dense_n / 64 bitmap words, all zero between launches; nullptr = the parked-row chain
