@@ -33,6 +33,11 @@ CMP_EQ, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE = range(6)
 
 # dbg_pred_op
 PRED_CMP_CONST, PRED_CMP_COLS, PRED_AND, PRED_OR, PRED_NOT, PRED_IS_NULL, PRED_IS_NOT_NULL, PRED_TRUE = range(8)
+PRED_LIKE = 16  # 8..15 are unassigned
+
+# dbg_like_kind, and the caps of a DBG_PRED_LIKE pattern
+LIKE_ORDINAL, LIKE_START_OF_PERCENT, LIKE_END_OF_PERCENT, LIKE_SURROUND_BY_PERCENT, LIKE_SIMPLE, LIKE_COMPLEX = range(6)
+LIKE_MAX_PATTERN, LIKE_MAX_SEGMENTS = 256, 16
 
 
 class dbg_datatype(C.Structure):

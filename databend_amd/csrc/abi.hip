@@ -302,11 +302,23 @@ int to_dcol(Owner o, const dbg_column& c, const dbg_datatype& want, bool check_t
     return DBG_OK;
 }
 
-int fill_filter(Owner o, const dbg_filter* f, int on_device, DCol* cols, int* ncols, DNode* nodes, int* nnodes) {
+// A DBG_PRED_LIKE node's pattern, classified (the checks of the header, shared with the host entry
+// points of abi_ops.hip)
+int like_check(const uint8_t* pat, uint64_t len, LikeDesc& L) {
+    if (!pat && len) return fail(DBG_ERR_INVALID, "LIKE: null pattern with a length");
+    if (len > DBG_LIKE_MAX_PATTERN)
+        return fail(DBG_ERR_UNSUPPORTED, "LIKE: patterns of at most " + std::to_string(DBG_LIKE_MAX_PATTERN) + " bytes");
+    if (!like_classify(pat, len, L))
+        return fail(DBG_ERR_UNSUPPORTED, "LIKE: at most " + std::to_string(DBG_LIKE_MAX_SEGMENTS) + " %-separated segments");
+    return DBG_OK;
+}
+
+int fill_filter(Owner o, const dbg_filter* f, int on_device, u64 rows, DCol* cols, int* ncols, DNode* nodes, int* nnodes) {
     if (f->n_cols > DBG_MAX_FCOLS || f->n_nodes > DBG_MAX_NODES) return fail(DBG_ERR_UNSUPPORTED, "filter too large");
     // predicates compare at most two words (cmp3_i128): no Decimal256 filter columns
     for (int c = 0; c < f->n_cols; ++c) REFUSE_DECIMAL256(f->cols[c].dt.type, "filter");
     int depth = 0;
+    LikeDesc likes[DBG_MAX_NODES];  // of the LIKE nodes, by node index
     for (int k = 0; k < f->n_nodes; ++k) {
         const dbg_pred_node& n = f->nodes[k];
         DNode& d = nodes[k];
@@ -319,9 +331,16 @@ int fill_filter(Owner o, const dbg_filter* f, int on_device, DCol* cols, int* nc
         d.f64v = n.f64;
         d.lo = n.i128_lo;
         d.hi = n.i128_hi;
-        if (n.op == DBG_PRED_CMP_CONST || n.op == DBG_PRED_CMP_COLS || n.op == DBG_PRED_IS_NULL || n.op == DBG_PRED_IS_NOT_NULL) {
+        if (n.op == DBG_PRED_CMP_CONST || n.op == DBG_PRED_CMP_COLS || n.op == DBG_PRED_IS_NULL || n.op == DBG_PRED_IS_NOT_NULL ||
+            n.op == DBG_PRED_LIKE) {
             if (n.col < 0 || n.col >= f->n_cols || (n.op == DBG_PRED_CMP_COLS && (n.col2 < 0 || n.col2 >= f->n_cols)))
                 return fail(DBG_ERR_INVALID, "predicate column index out of range");
+            if (n.op == DBG_PRED_LIKE) {
+                if (f->cols[n.col].dt.type != DBG_STRING) return fail(DBG_ERR_INVALID, "LIKE: the column is not a String column");
+                // the pre-pass reads offsets[0 .. rows] whatever the consumer kernel goes on to read
+                if (f->cols[n.col].len < rows) return fail(DBG_ERR_INVALID, "LIKE: filter column shorter than rows");
+                RETURN_IF(like_check(n.str, n.str_len, likes[k]));
+            }
             if (n.op == DBG_PRED_CMP_COLS) {  // cmp_cols reads both cells as the left column's type
                 const dbg_datatype &a = f->cols[n.col].dt, &b = f->cols[n.col2].dt;
                 if (a.type != b.type) return fail(DBG_ERR_INVALID, "column comparison: the two columns differ in type");
@@ -349,6 +368,24 @@ int fill_filter(Owner o, const dbg_filter* f, int on_device, DCol* cols, int* nc
     }
     if (f->n_nodes && depth != 1) return fail(DBG_ERR_INVALID, "malformed predicate program");
     for (int c = 0; c < f->n_cols; ++c) RETURN_IF(to_dcol(o, f->cols[c], f->cols[c].dt, false, on_device, cols[c]));
+    // LIKE nodes: the batch's match bitmap, rows / 8 bytes each, owned like the batch's other
+    // device copies (a retry, a rehash or the partitioned payload reads the predicate again later),
+    // filled on the stream before the kernel that evaluates the program
+    for (int k = 0; k < f->n_nodes; ++k) {
+        if (f->nodes[k].op != DBG_PRED_LIKE) continue;
+        const dbg_pred_node& n = f->nodes[k];
+        if (!cols[n.col].offsets) return fail(DBG_ERR_INVALID, "String column without offsets");
+        const void* p = nullptr;
+        RETURN_IF(own_copy(o, n.str, n.str_len, &p));
+        nodes[k].str = (const u8*)p;
+        nodes[k].str_len = n.str_len;
+        RETURN_IF(own_alloc(o, std::max<u64>(1, (rows + 63) / 64) * 8));
+        u64* const mask = (u64*)(u8*)o.owned.back();
+        nodes[k].mask = (const u8*)mask;
+        prof::Scope ps("like_mask", o.stream);
+        launch_like_mask(o.stream, cols[n.col], rows, likes[k], nodes[k].str, mask);
+        HIPCHECK(hipGetLastError());
+    }
     *ncols = f->n_cols;
     *nnodes = f->n_nodes;
     return DBG_OK;
@@ -422,7 +459,7 @@ static int add_groups_now(dbg_agg_handle* h, const dbg_column* group_cols, const
         if (arg_cols[a].len < rows) return fail(DBG_ERR_INVALID, "argument column shorter than rows");
         RETURN_IF(to_dcol(own, arg_cols[a], want, true, on_device, st->args[a]));
     }
-    if (filter && filter->n_nodes) RETURN_IF(fill_filter(own, filter, on_device, st->fcols, &st->n_fcols, st->nodes, &st->n_nodes));
+    if (filter && filter->n_nodes) RETURN_IF(fill_filter(own, filter, on_device, rows, st->fcols, &st->n_fcols, st->nodes, &st->n_nodes));
     RETURN_IF(submit_batch(h, &st, &bid, on_device && h->owned.size() == owned0));
     // high cardinality: the radix-partitioned payload instead of the HBM table (pp.hip)
     if (!h->pp) RETURN_IF(pp_maybe_switch(h, bid, rows));

@@ -24,6 +24,7 @@
 #include "serde.hpp"
 
 #include "filter.hpp"
+#include "like.hpp"
 #include "sort.hpp"
 #include "prof.hpp"
 
@@ -313,7 +314,9 @@ int err_bits_fail(u64 err, u64 mask);
 int own_alloc(Owner o, size_t bytes);  // o.owned.back(): `bytes` of device memory
 DCol dcol_view(const dbg_column& c);   // a caller's device-resident column as the kernels read it
 int to_dcol(Owner o, const dbg_column& c, const dbg_datatype& want, bool check_type, int on_device, DCol& d);
-int fill_filter(Owner o, const dbg_filter* f, int on_device, DCol* cols, int* ncols, DNode* nodes, int* nnodes);
+// rows: the batch's rows (the match bitmap of every DBG_PRED_LIKE node is filled on o.stream, like.hip)
+int fill_filter(Owner o, const dbg_filter* f, int on_device, u64 rows, DCol* cols, int* ncols, DNode* nodes, int* nnodes);
+int like_check(const uint8_t* pat, uint64_t len, LikeDesc& L);  // a LIKE pattern within the header's caps, classified
 TableDesc table_desc(dbg_agg_handle* h);
 int flush_deferred(dbg_agg_handle* h);
 int part_flush(dbg_agg_handle* h);

@@ -1,7 +1,7 @@
 // abi_ops.hip — the entry points that take no handle: the standalone filter (dbg_filter_select),
-// take (dbg_take_*), the legacy hash methods (dbg_legacy_*), sort with limit (dbg_sort_limit_*) and
-// the workload generator (dbg_datagen).  Each works on the caller's device columns and stream and
-// keeps nothing; the kernels are filter.hip, legacy.hip, sort.hip and datagen.hip.
+// LIKE's host entry points (dbg_like_*), take (dbg_take_*), the legacy hash methods (dbg_legacy_*),
+// sort with limit (dbg_sort_limit_*) and the workload generator (dbg_datagen).  Each works on the caller's device columns and stream and
+// keeps nothing; the kernels are filter.hip, like.hip, legacy.hip, sort.hip and datagen.hip.
 #include "abi_internal.hpp"
 
 // HashMethodKind::choose_hash_method_with_types (EXP/kernels/group_by.rs:48-97)
@@ -53,11 +53,11 @@ int dbg_filter_select(const dbg_filter* filter, uint64_t rows, uint32_t* sel_out
     if (!filter || !sel_out || !n_sel) return fail(DBG_ERR_INVALID, "null argument");
     if (rows >= 0xFFFFFFFFULL) return fail(DBG_ERR_UNSUPPORTED, "selection indices are u32");
     hipStream_t s = (hipStream_t)stream;
-    std::vector<DevBuf> consts;  // device copies of the predicates' string constants
+    std::vector<DevBuf> consts;  // device copies of the predicates' string constants, and the LIKE nodes' match bitmaps
     FilterDesc fd;
     memset(&fd, 0, sizeof(fd));
     fd.rows = rows;
-    RETURN_IF(fill_filter({s, consts}, filter, 1, fd.cols, &fd.n_cols, fd.nodes, &fd.n_nodes));
+    RETURN_IF(fill_filter({s, consts}, filter, 1, rows, fd.cols, &fd.n_cols, fd.nodes, &fd.n_nodes));
     Buf<FilterDesc> dfd;
     Buf<u64> scratch;
     u64 nb = filter_blocks(rows);
@@ -73,6 +73,37 @@ int dbg_filter_select(const dbg_filter* filter, uint64_t rows, uint32_t* sel_out
     hipError_t e = hipStreamSynchronize(s);  // the kernel has read dfd, scratch and the constants
     *n_sel = tot;
     if (e != hipSuccess) return fail(DBG_ERR_DEVICE, std::string("filter: ") + hipGetErrorString(e));
+    return DBG_OK;
+}
+
+// ---- LIKE on the host: the classification and the host build of the kernels' matcher (like.hpp) ----
+int dbg_like_pattern_kind(const uint8_t* pat, uint64_t len, int32_t* kind) {
+    if (!kind) return fail(DBG_ERR_INVALID, "null argument");
+    LikeDesc L;
+    RETURN_IF(like_check(pat, len, L));
+    *kind = L.kind;
+    return DBG_OK;
+}
+
+int dbg_like_match_host(const uint8_t* str, uint64_t len, const uint8_t* pat, uint64_t plen, int32_t* out) {
+    if (!out || (!str && len)) return fail(DBG_ERR_INVALID, "null argument");
+    LikeDesc L;
+    RETURN_IF(like_check(pat, plen, L));
+    *out = like_match(L, str, len, pat) ? 1 : 0;
+    return DBG_OK;
+}
+
+int dbg_like_kernel_counts(uint64_t* counts, int32_t n) {
+    if (!counts || n < 0) return fail(DBG_ERR_INVALID, "null argument");
+    u64 c[LIKE_K_N];
+    like_kernel_counts(c);
+    for (int32_t i = 0; i < n; ++i) counts[i] = i < LIKE_K_N ? c[i] : 0;
+    return DBG_OK;
+}
+
+int dbg_like_force_kernel(int32_t kernel) {
+    if (kernel != 0 && kernel != LIKE_K_ROWS && kernel != LIKE_K_SCAN) return fail(DBG_ERR_INVALID, "dbg_like_force_kernel: 0, 1 (rows) or 2 (scan)");
+    like_force_kernel(kernel);
     return DBG_OK;
 }
 

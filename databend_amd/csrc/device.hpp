@@ -298,6 +298,9 @@ struct DNode {
     i64 hi;
     const u8* str;  // device copy of the constant
     u64 str_len;
+    // DBG_PRED_LIKE: the batch's match bitmap, bit i = row i matches the pattern (a pre-pass on
+    // the same stream fills it before the kernel that evaluates the program, like.hip)
+    const u8* mask;
 };
 
 __device__ __forceinline__ int cmp3_i64(i64 a, i64 b) { return a < b ? -1 : (a > b ? 1 : 0); }
@@ -391,6 +394,9 @@ __device__ __forceinline__ bool eval_pred(const DNode* nodes, int n_nodes, const
                 break;
             case DBG_PRED_IS_NULL: v = dcol_valid(cols[n.col], i) ? 0u : 1u; break;
             case DBG_PRED_IS_NOT_NULL: v = dcol_valid(cols[n.col], i) ? 1u : 0u; break;
+            case DBG_PRED_LIKE:
+                v = !dcol_valid(cols[n.col], i) ? 2u : ((gld<u8>(n.mask + (i >> 3)) >> (i & 7)) & 1u);
+                break;
             case DBG_PRED_NOT: {
                 u32 a = (st >> (2 * (sp - 1))) & 3u;
                 sp -= 1;

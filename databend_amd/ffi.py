@@ -28,7 +28,7 @@ EXPORTED = [
     "dbg_payload_exchange_plan", "dbg_merge_exchange_plan", "dbg_agg_payload_counts_from", "dbg_agg_payload_export_from",
     "dbg_agg_payload_import_chunks", "dbg_agg_exchange_payload_chunk",
     "dbg_scan_create", "dbg_scan_destroy", "dbg_parquet_chunk_rows", "dbg_parquet_decode",
-    "dbg_native_decode",
+    "dbg_native_decode", "dbg_like_pattern_kind", "dbg_like_match_host", "dbg_like_kernel_counts", "dbg_like_force_kernel",
 ]
 
 
@@ -134,6 +134,10 @@ def lib():
                                          P(U64)]
         L.dbg_native_decode.argtypes = [VP, P(abi.dbg_native_column), abi.dbg_datatype, P(abi.dbg_out_column), U64, U64, P(U64),
                                         P(U64)]
+        L.dbg_like_pattern_kind.argtypes = [C.c_char_p, U64, P(I32)]
+        L.dbg_like_match_host.argtypes = [C.c_char_p, U64, C.c_char_p, U64, P(I32)]
+        L.dbg_like_kernel_counts.argtypes = [P(U64), I32]
+        L.dbg_like_force_kernel.argtypes = [I32]
         L.dbg_datagen.argtypes = [C.c_int, U64, U64, U64, P(VP), C.c_int, VP, VP]
         _LIB = L
     return _LIB

@@ -7,6 +7,7 @@ u32 selection vector (selector.rs:64-325).  Here the same tree is flattened to a
 only when the predicate is TRUE, filter_executor.rs:73-128).
 
     pred = and_(cmp(0, "<=", 10471), not_(is_null(1)))
+    pred = and_(like(0, "%google%"), cmp(1, "<>", ""))
 """
 from __future__ import annotations
 
@@ -61,6 +62,15 @@ class _Un(Pred):
         return [dict(op=self.op, col=self.col)]
 
 
+class _Like(Pred):
+    def __init__(self, col: int, pattern):
+        self.col = col
+        self.pattern = pattern.encode() if isinstance(pattern, str) else bytes(pattern)
+
+    def postfix(self):
+        return [dict(op=abi.PRED_LIKE, col=self.col, pattern=self.pattern)]
+
+
 def cmp(col: int, op: str, const) -> Pred:
     return _Cmp(col, op, const)
 
@@ -95,6 +105,17 @@ def is_not_null(col: int) -> Pred:
     return _Un(abi.PRED_IS_NOT_NULL, col=col)
 
 
+def like(col: int, pattern) -> Pred:
+    """`col LIKE pattern` (SelectExpr::Like, select_expr.rs:147-180): the raw pattern as SQL gave it,
+    escapes not pre-processed; NULL where the cell is NULL."""
+    return _Like(col, pattern)
+
+
+def not_like(col: int, pattern) -> Pred:
+    """`col NOT LIKE pattern`: the reference's `not` flag is NOT over the node under three-valued logic."""
+    return not_(like(col, pattern))
+
+
 def true_() -> Pred:
     return _Un(abi.PRED_TRUE)
 
@@ -120,6 +141,10 @@ class FilterProgram:
             n.col2 = d.get("col2", 0)
             if "const" in d:
                 self._set_const(n, self.cols[n.col], d["const"])
+            if "pattern" in d:
+                if 0 <= n.col < len(self.cols) and self.cols[n.col].dt.type != abi.STRING:  # as the library refuses it
+                    raise DbgError(abi.DBG_ERR_INVALID, "LIKE: the column is not a String column")
+                self._set_bytes(n, d["pattern"])
             if n.op == abi.PRED_CMP_COLS and max(n.col, n.col2) < len(self.cols) and min(n.col, n.col2) >= 0:
                 a, b = self.cols[n.col].dt, self.cols[n.col2].dt  # the library refuses the same way (fill_filter)
                 if a.type != b.type:
@@ -132,11 +157,7 @@ class FilterProgram:
     def _set_const(self, n: abi.dbg_pred_node, col: abi.dbg_column, v):
         t = col.dt.type
         if t == abi.STRING:
-            b = v.encode() if isinstance(v, str) else bytes(v)
-            buf = C.create_string_buffer(b, max(1, len(b)))
-            self._keep.append(buf)
-            n.str = C.addressof(buf)
-            n.str_len = len(b)
+            self._set_bytes(n, v.encode() if isinstance(v, str) else bytes(v))
         elif t in (abi.FLOAT32, abi.FLOAT64):
             n.f64 = float(v)
         elif t == abi.DECIMAL128:
@@ -155,6 +176,12 @@ class FilterProgram:
             n.i64 = u - (1 << 64) if u >= (1 << 63) else u
         else:
             n.i64 = int(v)
+
+    def _set_bytes(self, n: abi.dbg_pred_node, b: bytes):
+        buf = C.create_string_buffer(b, max(1, len(b)))
+        self._keep.append(buf)
+        n.str = C.addressof(buf)
+        n.str_len = len(b)
 
     def ptr(self):
         return C.byref(self.struct)

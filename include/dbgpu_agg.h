@@ -134,8 +134,34 @@ typedef enum {
     DBG_PRED_NOT = 4,       /* pops 1 */
     DBG_PRED_IS_NULL = 5,
     DBG_PRED_IS_NOT_NULL = 6,
-    DBG_PRED_TRUE = 7
+    DBG_PRED_TRUE = 7,
+    /* 8..15 are unassigned and refused as "unknown predicate op". */
+    /* column LIKE 'pattern' (SelectExpr::Like, EXP/filter/select_expr.rs:147-180, run by
+     * Selector::process_like, selector.rs:325-369, with the matchers of EXP/filter/like.rs).
+     * col: a String or nullable String column; str / str_len: the raw pattern bytes exactly as SQL
+     * gave them (escapes are not pre-processed; the pattern is classified by
+     * generate_like_pattern's rules, see dbg_like_pattern_kind).  Value: NULL where the cell is
+     * NULL, otherwise TRUE / FALSE by the reference's match — so a NULL cell is selected by neither
+     * LIKE nor NOT LIKE, as the reference's `validity && ...` has it.  NOT LIKE is DBG_PRED_NOT
+     * over this node (the reference's `not` flag is the same under three-valued logic).
+     * Refused: a column that is not String, or str == NULL with str_len > 0 (DBG_ERR_INVALID); a
+     * pattern of more than DBG_LIKE_MAX_PATTERN bytes, or a SimplePattern of more than
+     * DBG_LIKE_MAX_SEGMENTS '%'-separated segments (DBG_ERR_UNSUPPORTED). */
+    DBG_PRED_LIKE = 16
 } dbg_pred_op;
+
+#define DBG_LIKE_MAX_PATTERN 256 /* pattern bytes */
+#define DBG_LIKE_MAX_SEGMENTS 16 /* non-empty '%'-separated segments of a SimplePattern */
+
+/* LikePattern (EXP/filter/like.rs:18-33) */
+typedef enum {
+    DBG_LIKE_ORDINAL = 0,             /* no '%': equality with the raw pattern */
+    DBG_LIKE_START_OF_PERCENT = 1,    /* '%abc': ends_with */
+    DBG_LIKE_END_OF_PERCENT = 2,      /* 'abc%': starts_with */
+    DBG_LIKE_SURROUND_BY_PERCENT = 3, /* '%abc%': substring; '%%' matches everything */
+    DBG_LIKE_SIMPLE = 4,              /* only '%' wildcards, e.g. 'a%b%c'; never matches '' */
+    DBG_LIKE_COMPLEX = 5              /* '_' or an escaped wildcard: backtracking matcher */
+} dbg_like_kind;
 
 typedef struct dbg_pred_node {
     int32_t op;   /* dbg_pred_op */
@@ -567,6 +593,19 @@ int dbg_agg_merge_fixed(dbg_agg_handle* h, const void* dev_bufs, int32_t n_bufs,
  * *n_sel its count (synchronous). */
 int dbg_filter_select(const dbg_filter* filter, uint64_t rows, uint32_t* sel_out, uint64_t* n_sel,
                       void* hip_stream);
+/* ---- LIKE on the host (no device needed): the classification and the matcher the kernels run ----
+ * dbg_like_pattern_kind: *kind = the dbg_like_kind generate_like_pattern (EXP/filter/like.rs:186-248)
+ * gives the raw pattern.  dbg_like_match_host: *out = 1 when str LIKE pat by the reference's
+ * matcher for that class, else 0 (the host build of the source the kernels compile).  Both refuse a
+ * pattern beyond the caps of DBG_PRED_LIKE with DBG_ERR_UNSUPPORTED. */
+int dbg_like_pattern_kind(const uint8_t* pat, uint64_t len, int32_t* kind);
+int dbg_like_match_host(const uint8_t* str, uint64_t len, const uint8_t* pat, uint64_t plen, int32_t* out);
+/* How often each LIKE mask pre-pass ran in this process, for tests and benchmarks: counts[0]
+ * all-ones fill ('%%'), [1] like_rows_kernel, [2] like_scan_kernel.  dbg_like_force_kernel(1 | 2)
+ * makes every later '%needle%' mask of this process come from like_rows_kernel / like_scan_kernel,
+ * 0 restores the library's own choice: a result-neutral hook for tests and measurements. */
+int dbg_like_kernel_counts(uint64_t* counts, int32_t n);
+int dbg_like_force_kernel(int32_t kernel);
 /* DataBlock::take (EXP/kernels/take.rs:56-91) of one fixed-width column on device:
  * out[i] = in[sel[i]] (value bytes; validity gathered into out_validity bit-packed when non-NULL). */
 int dbg_take_fixed(const dbg_column* col, const uint32_t* sel, uint64_t n_sel, void* out_data,
