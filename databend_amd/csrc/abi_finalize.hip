@@ -1,6 +1,7 @@
 // abi_finalize.hip — both finalize families of a handle: dbg_agg_finalize + dbg_agg_result[_serialized]
 // (sizes first, then the columns), and dbg_agg_finalize_into[_async] / dbg_agg_finalize_wait (the
-// caller's buffers, one fused round: fin_setup / fin_launch / fin_complete).  The table's growth
+// caller's buffers, one fused round: fin_setup / fin_launch / fin_complete), with dbg_agg_step_async
+// (reset + device batch + that round's launch in one call).  The table's growth
 // and overflow are abi.hip's, the partitioned payload's ends of both families abi_pp.hip's.
 #include "abi_exp.hpp"
 
@@ -325,6 +326,7 @@ static int fin_launch(dbg_agg_handle* h) {
         h->def_on = false;
         prof::Scope ps("agg_insert", h->stream);
         note_insert(h, launch_insert(h->stream, h->dspec, S, h->dbatches, h->def_bid, h->def_rows, false, t, true, &h->def_hb, &ff));
+        exp_launch_returned();
     } else if (small) {
         prof::Scope ps("finalize_small", h->stream);
         launch_finalize_small(h->stream, h->dspec, h->dbatches, t, od, totals, F.zero_copy ? h->hcounters_dev : nullptr,
@@ -380,7 +382,8 @@ static int fin_complete(dbg_agg_handle* h, bool* retry, uint64_t* n_groups, uint
             if ((it & 255) == 255 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) break;
             __builtin_ia32_pause();
         }
-        if (!seen) HIPCHECK(hipStreamSynchronize(h->stream));
+        if (seen) exp_completion_seen();
+        else HIPCHECK(hipStreamSynchronize(h->stream));
         HIPCHECK(hipGetLastError());
         recycled = h->hcounters[CNT_WORDS + 1 + DBG_MAX_KEYS] != 0;
     }
@@ -531,6 +534,22 @@ int dbg_agg_finalize_into_async(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg
         return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_agg_finalize_into_async: ") + handle_local_reason(h->spec));
     if (h->fin.active) return fail(DBG_ERR_INVALID, "a finalize is already in flight: dbg_agg_finalize_wait first");
     HIPCHECK(hipSetDevice(h->device));
+    RETURN_IF(fin_setup(h, out_aggs, out_keys, max_groups, max_string_bytes));
+    return fin_launch(h);
+}
+
+// One device batch into result columns: dbg_agg_reset + dbg_agg_add_groups(on_device = 1) +
+// dbg_agg_finalize_into_async in one crossing.  What finalize_into_async would refuse is refused
+// before the reset, so a refused call leaves the handle (and a finalize in flight) as it was.
+int dbg_agg_step_async(dbg_agg_handle* h, const dbg_column* group_cols, const dbg_column* arg_cols, const dbg_filter* filter,
+                       uint64_t rows, dbg_out_column* out_aggs, dbg_out_column* out_keys, uint64_t max_groups,
+                       const uint64_t* max_string_bytes) {
+    if (!h || !group_cols || !out_aggs || !out_keys) return fail(DBG_ERR_INVALID, "null argument");
+    if (has_str_minmax(h->spec))
+        return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_agg_step_async: ") + handle_local_reason(h->spec));
+    if (h->fin.active) return fail(DBG_ERR_INVALID, "a finalize is already in flight: dbg_agg_finalize_wait first");
+    RETURN_IF(dbg_agg_reset(h));
+    RETURN_IF(dbg_agg_add_groups(h, group_cols, arg_cols, filter, rows, 1));
     RETURN_IF(fin_setup(h, out_aggs, out_keys, max_groups, max_string_bytes));
     return fin_launch(h);
 }

@@ -2876,13 +2876,16 @@ __device__ __forceinline__ T vget(const v4u& y, int j) {
 template <typename T, bool PRED, int NT, bool CO>
 __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restrict__ spec, const BatchDesc* __restrict__ batches,
                                                                u32 bid, u64 rows, TableDesc t, u32 lds_slots,
-                                                               T lo, T hi, int negate, FusedFin ff) {
+                                                               T lo, T hi, int negate, FusedFin ff, const void* key0,
+                                                               u32 stride_words) {
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
     constexpr int V = 16 / sizeof(T);
     const Spec& S = *spec;
     const BatchDesc& B = batches[bid];
-    const T* __restrict__ col = (const T*)B.keys[0].data;
-    const u32 sw = S.stride_words;
+    // The key column's base (B.keys[0].data) and S.stride_words come by value: the stream's first
+    // loads then depend on the kernel arguments alone, not on two cold descriptor reads.
+    const T* __restrict__ col = (const T*)key0;
+    const u32 sw = stride_words;
     u32* lcount = (u32*)(lds + (u64)lds_slots * sw);
     const u32 lmask = lds_slots - 1;
     const u32 llimit = lds_slots - lds_slots / 4;
@@ -2894,9 +2897,41 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
     v4u* vq = (v4u*)qkey;
     u64* vqb = qkey + 2 * WQ;
     if (kPhaseTrace && ff.trace && threadIdx.x == 0) atomicMin((unsigned long long*)ff.trace, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    // Grid-strided stream (all waves of the chip sweep one window of the column together: DRAM
+    // rows stay open, scripts/micro/stream.hip): FAST_UNROLL unconditional 16-byte loads per lane
+    // per round (an index past the end is clamped and its lane-slot masked off), so no branch
+    // sits around the loads; other waves of the CU keep HBM busy while one filters.
+    const u64 nvec = rows / V;
+    gv4p vp = (gv4p)col;
+    const u64 gstride = (u64)gridDim.x * NT;
+    u64 k = (u64)blockIdx.x * NT + threadIdx.x;
+    const u64 step = (u64)FAST_UNROLL * gstride;
+    const u64 lastv = nvec ? nvec - 1 : 0;
+    // Dynamic tail (fused-chain launches): the grid-strided static part covers ~80 % of the
+    // vectors in whole rounds of the grid; the rest is cut into chunks of NT x FAST_UNROLL vectors
+    // that workgroups done with their static share take from a device counter — so the chip's
+    // fast CUs absorb the end of the stream instead of waiting for its slow ones (workgroups
+    // finished streaming between 27.8 and 35.0 us of a C2 launch, DESIGN.md §4.3).  The counter
+    // (CNT_TAIL) is reset by the launch's last group leader.
+    constexpr u64 TAIL_CH = (u64)NT * FAST_UNROLL;
+    const bool dyn = TAIL_ON && ff.on && t.scratch != nullptr && gridDim.x > 1 && gridDim.x <= t.scr_blocks;
+    u64 nstat = nvec, nch = 0;
+    if (dyn) {
+        nstat = ((nvec * 4 / 5) / step) * step;
+        nch = (nvec - nstat + TAIL_CH - 1) / TAIL_CH;
+    }
+    // The first round's loads go out before the LDS table is initialised: they need nothing but
+    // the kernel arguments, and the barrier below waits for LDS only, so they stay in flight
+    // across the initialisation (one memory trip earlier on every CU's hand-over between launches).
+    v4u y[FAST_UNROLL];
+#pragma unroll
+    for (int u = 0; u < FAST_UNROLL; ++u) {
+        u64 idx = k + u * gstride;
+        y[u] = __builtin_nontemporal_load(vp + (idx < nstat ? idx : lastv));
+    }
     lds_table_init<false>(S, lds, lds_slots, sw, NT);
     if (threadIdx.x < 4) lcount[threadIdx.x] = 0;
-    __syncthreads();
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // LDS only: the loads above stay in flight
     u32 my_claims = 0;
     u32 my_ovf = 0;  // overflow rows pushed (the fused chain reports them through its tickets)
 
@@ -3091,41 +3126,13 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
         }
     };
 
-    // Grid-strided stream (all waves of the chip sweep one window of the column together: DRAM
-    // rows stay open, scripts/micro/stream.hip): FAST_UNROLL unconditional 16-byte loads per lane
-    // per round (an index past the end is clamped and its lane-slot masked off), so no branch
-    // sits around the loads; other waves of the CU keep HBM busy while one filters.  The loop
-    // condition is wave-uniform (ballot) because the queue needs all 64 lanes.
-    const u64 nvec = rows / V;
-    gv4p vp = (gv4p)col;
-    const u64 gstride = (u64)gridDim.x * NT;
-    u64 k = (u64)blockIdx.x * NT + threadIdx.x;
-    const u64 step = (u64)FAST_UNROLL * gstride;
-    const u64 lastv = nvec ? nvec - 1 : 0;
-    // Dynamic tail (fused-chain launches): the grid-strided static part covers ~80 % of the
-    // vectors in whole rounds of the grid; the rest is cut into chunks of NT x FAST_UNROLL vectors
-    // that workgroups done with their static share take from a device counter — so the chip's
-    // fast CUs absorb the end of the stream instead of waiting for its slow ones (workgroups
-    // finished streaming between 27.8 and 35.0 us of a C2 launch, DESIGN.md §4.3).  The counter
-    // (CNT_TAIL) is reset by the launch's last group leader.
-    constexpr u64 TAIL_CH = (u64)NT * FAST_UNROLL;
-    const bool dyn = TAIL_ON && ff.on && t.scratch != nullptr && gridDim.x > 1 && gridDim.x <= t.scr_blocks;
-    u64 nstat = nvec, nch = 0;
-    if (dyn) {
-        nstat = ((nvec * 4 / 5) / step) * step;
-        nch = (nvec - nstat + TAIL_CH - 1) / TAIL_CH;
-    }
     u64 tail_grab = 0;  // thread 0: the first tail chunk, taken now (its latency hides behind the stream)
     if (dyn && nch && threadIdx.x == 0) tail_grab = atomicAdd((unsigned long long*)(t.counters + CNT_TAIL), 1ULL);
     // Software pipeline: the next round's FAST_UNROLL loads are issued before this round is
-    // filtered and queued, so a wave busy with its ballots and LDS queue writes still has
-    // 64 B/lane in flight (without it the per-round processing sits on the load critical path).
-    v4u y[FAST_UNROLL];
-#pragma unroll
-    for (int u = 0; u < FAST_UNROLL; ++u) {
-        u64 idx = k + u * gstride;
-        y[u] = __builtin_nontemporal_load(vp + (idx < nstat ? idx : lastv));
-    }
+    // filtered and queued (the first round's went out before the table's initialisation), so a
+    // wave busy with its ballots and LDS queue writes still has 64 B/lane in flight (without it
+    // the per-round processing sits on the load critical path).  The loop condition is
+    // wave-uniform (ballot) because the queue needs all 64 lanes.
     while (__ballot(k < nstat) != 0) {
         const u64 kn = k + step;
         v4u yn[FAST_UNROLL];
@@ -3243,8 +3250,9 @@ static size_t fast_shmem(size_t table_bytes) { return table_bytes + (size_t)(102
 static size_t fast_table_bytes(const Spec& S) { return (size_t)lds_slots_for(S, 16 * 1024) * S.stride_words * 8 + 16; }
 
 template <typename T>
-static void launch_fast_t(hipStream_t s, const Spec* dspec, const BatchDesc* batches, u32 bid, u64 rows, const TableDesc& t,
-                          u32 lslots, size_t table_bytes, bool pred, int op, i64 c, int count_only, const FusedFin* fused) {
+static void launch_fast_t(hipStream_t s, const Spec* dspec, const Spec& S, const void* key0, const BatchDesc* batches, u32 bid, u64 rows,
+                          const TableDesc& t, u32 lslots, size_t table_bytes, bool pred, int op, i64 c, int count_only,
+                          const FusedFin* fused) {
     constexpr u64 V = 16 / sizeof(T);
     // `v <op> c` as `(lo <= v <= hi) ^ negate`, exact over T's range (constants outside it fold)
     typedef __int128 W;
@@ -3291,10 +3299,10 @@ static void launch_fast_t(hipStream_t s, const Spec* dspec, const BatchDesc* bat
     do {                                                                                                                         \
         if (ext)                                                                                                                 \
             hipExtLaunchKernelGGL((agg_insert_fast_kernel<T, P, N, F>), dim3((u32)blocks), dim3(N), shmem, s, ev0, ev1, 0, dspec, \
-                                  batches, bid, rows, t, lslots, (T)lo, (T)hi, neg, ff);                                        \
+                                  batches, bid, rows, t, lslots, (T)lo, (T)hi, neg, ff, key0, (u32)S.stride_words);             \
         else                                                                                                                     \
             hipLaunchKernelGGL((agg_insert_fast_kernel<T, P, N, F>), dim3((u32)blocks), dim3(N), shmem, s, dspec, batches, bid, \
-                               rows, t, lslots, (T)lo, (T)hi, neg, ff);                                                          \
+                               rows, t, lslots, (T)lo, (T)hi, neg, ff, key0, (u32)S.stride_words);                               \
     } while (0)
     // CO: COUNT(*) is the only aggregate (ClickBench Q8/Q16 shape) — the kernel then carries no
     // apply_row code at all (smaller hot loop, fewer registers)
@@ -3345,14 +3353,14 @@ InsertPath launch_insert(hipStream_t s, const Spec* dspec, const Spec& S, const 
         int count_only = S.n_aggs == 1 && S.aggs[0].kind == DBG_AGG_COUNT && S.aggs[0].arg_type < 0 && S.aggs[0].w0 == 1;
         const InsertPath path = pred ? INS_FAST_PRED : INS_FAST;
         switch (hb->keys[0].type) {
-            case DBG_INT8: launch_fast_t<int8_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
-            case DBG_UINT8: launch_fast_t<uint8_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
-            case DBG_INT16: launch_fast_t<int16_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
-            case DBG_UINT16: launch_fast_t<uint16_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
-            case DBG_INT32: case DBG_DATE: launch_fast_t<int32_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
-            case DBG_UINT32: launch_fast_t<uint32_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
-            case DBG_INT64: case DBG_TIMESTAMP: launch_fast_t<int64_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
-            case DBG_UINT64: launch_fast_t<uint64_t>(s, dspec, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_INT8: launch_fast_t<int8_t>(s, dspec, S, hb->keys[0].data, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_UINT8: launch_fast_t<uint8_t>(s, dspec, S, hb->keys[0].data, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_INT16: launch_fast_t<int16_t>(s, dspec, S, hb->keys[0].data, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_UINT16: launch_fast_t<uint16_t>(s, dspec, S, hb->keys[0].data, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_INT32: case DBG_DATE: launch_fast_t<int32_t>(s, dspec, S, hb->keys[0].data, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_UINT32: launch_fast_t<uint32_t>(s, dspec, S, hb->keys[0].data, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_INT64: case DBG_TIMESTAMP: launch_fast_t<int64_t>(s, dspec, S, hb->keys[0].data, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
+            case DBG_UINT64: launch_fast_t<uint64_t>(s, dspec, S, hb->keys[0].data, batches, bid, rows, t, lslots, shmem, pred, op, c, count_only, fused); return path;
         }
     }
     // one non-null String key into a large key-caching table, filtered by `key <op> ''` or not

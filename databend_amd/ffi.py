@@ -19,7 +19,7 @@ _LIB = None
 EXPORTED = [
     "dbg_version", "dbg_last_error", "dbg_device_count", "dbg_agg_result_type", "dbg_agg_create",
     "dbg_agg_destroy", "dbg_agg_set_stream", "dbg_agg_reset", "dbg_agg_add_groups", "dbg_agg_finalize",
-    "dbg_agg_result", "dbg_agg_finalize_into", "dbg_agg_set_recycle", "dbg_agg_set_partition_keys", "dbg_agg_finalize_into_async", "dbg_agg_finalize_wait", "dbg_agg_record_width", "dbg_agg_partition", "dbg_agg_export_records",
+    "dbg_agg_result", "dbg_agg_finalize_into", "dbg_agg_set_recycle", "dbg_agg_set_partition_keys", "dbg_agg_finalize_into_async", "dbg_agg_finalize_wait", "dbg_agg_step_async", "dbg_agg_record_width", "dbg_agg_partition", "dbg_agg_export_records",
     "dbg_agg_merge_records", "dbg_agg_export_fixed", "dbg_agg_capacity", "dbg_agg_merge_fixed", "dbg_filter_select", "dbg_take_fixed", "dbg_sort_limit_indices", "dbg_sort_limit_multi", "dbg_agg_compact", "dbg_agg_retained_bytes", "dbg_prof_enable", "dbg_prof_reset",
     "dbg_prof_get", "dbg_prof_marker", "dbg_datagen", "dbg_agg_set_strategy", "dbg_agg_get_strategy", "dbg_agg_get_pp_stats", "dbg_agg_insert_paths",
     "dbg_agg_record_layout", "dbg_agg_set_host_staging", "dbg_agg_result_string_bytes",
@@ -93,6 +93,8 @@ def lib():
         L.dbg_agg_insert_paths.argtypes = [VP, P(U64), I32]
         L.dbg_agg_finalize_into_async.argtypes = [VP, P(abi.dbg_out_column), P(abi.dbg_out_column), U64, P(U64)]
         L.dbg_agg_finalize_wait.argtypes = [VP, P(U64), P(U64)]
+        L.dbg_agg_step_async.argtypes = [VP, P(abi.dbg_column), P(abi.dbg_column), P(abi.dbg_filter), U64, P(abi.dbg_out_column),
+                                         P(abi.dbg_out_column), U64, P(U64)]
         L.dbg_agg_record_width.argtypes = [VP, P(C.c_uint32)]
         L.dbg_agg_partition.argtypes = [VP, C.c_uint32, C.c_int, P(U64), P(U64)]
         L.dbg_agg_export_records.argtypes = [VP, VP, VP]

@@ -329,6 +329,21 @@ int dbg_agg_finalize_into_async(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg
                                 uint64_t max_groups, const uint64_t* max_string_bytes);
 int dbg_agg_finalize_wait(dbg_agg_handle* h, uint64_t* n_groups, uint64_t* string_bytes);
 
+/* One device-resident batch aggregated into result columns, in one call: exactly dbg_agg_reset +
+ * dbg_agg_add_groups(..., on_device = 1) + dbg_agg_finalize_into_async, with their errors and
+ * fallbacks (a shape whose insert cannot fuse with the finalize gives what the three calls give).
+ * dbg_agg_finalize_wait completes it, short-buffer and overflow retries included.  This is the
+ * per-block call of a host that keeps several independent handles in flight, each on its own
+ * stream: step handle A, step handle B, wait A, step A, wait B, ...  — between two waits the host
+ * crosses the interface once, so the next batch is queued while the previous one still runs.
+ * What dbg_agg_finalize_into_async refuses (a finalize already in flight, a String MIN/MAX
+ * aggregate) is refused before the reset: the handle, its groups and the finalize in flight stay
+ * as they were.  In recycle mode the input columns must stay unchanged until the batch's
+ * dbg_agg_finalize_wait returns. */
+int dbg_agg_step_async(dbg_agg_handle* h, const dbg_column* group_cols, const dbg_column* arg_cols,
+                       const dbg_filter* filter, uint64_t rows, dbg_out_column* out_aggs, dbg_out_column* out_keys,
+                       uint64_t max_groups, const uint64_t* max_string_bytes);
+
 /* Recycle mode (default off): a dbg_agg_finalize_into that delivers every group of a small table
  * (low cardinality, finalized in one workgroup) also re-initialises the table in that same
  * launch, leaving the handle as dbg_agg_reset would — the result columns are then the only copy
