@@ -213,11 +213,10 @@ struct dbg_agg_handle {
         u8* alt = nullptr;  // alias
     } ppk[2];
     u32 pp_bits = 0;  // final partition bits
-    u32 pp_rc_sub = 0;  // > 0: record-centric aggregation in 2^pp_rc_sub rounds per partition (pp.hip)
     int pp_spec = -1;   // >= 0: the compile-time specialised aggregation's shape (pp_agg_spec_kernel)
     u32 pp_spec_sub = 0;  // its rounds per partition: 2^pp_spec_sub
-    // [count, partition ids...] spilled by the specialised / record-centric kernel: an id per final
-    // partition, so no spill is ever dropped
+    // [count, partition ids...] spilled by the specialised kernel: an id per final partition, so
+    // no spill is ever dropped
     Buf<u32> pp_spill;
     Buf<u32> pp_cnt;
     Buf<u64> pp_off;

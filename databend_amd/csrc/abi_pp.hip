@@ -275,36 +275,13 @@ static int pp_prepare(dbg_agg_handle* h, bool spec_ok) {
     while ((double)(1ULL << B) < need && B < PP_L1_BITS + 16) ++B;
     // level 2 takes up to 10 bits (one pass instead of a 1-2 bit third level), level 3 the rest
     u32 k2 = std::min<u32>(B - PP_L1_BITS <= 10 ? 10 : 8, B - PP_L1_BITS), k3 = B - PP_L1_BITS - k2;
-    // Record-centric aggregation (raw records only): one workgroup per level-2 partition (sized
-    // here for ~PP_RC_PART records on average), aggregated in 2^sub rounds of at most ~0.7 of one
-    // LDS round's records — no level 3.
-    h->pp_rc_sub = 0;
-    // measured slower than the slot-table kernel on C4 (pp_agg 74 vs 58 ms): opt-in (DBG_X_PPRC=1)
-    static const bool rc_on = X_ENV("DBG_X_PPRC") && X_ENV("DBG_X_PPRC")[0] == '1';
-    if (rc_on && pp_rc_ok(S) && nsr == 0 && nr > 0) {
-        const double per_part = (double)PP_RC_PART;
-        u32 b2 = PP_L1_BITS + 1;
-        while ((double)nr / (double)(1ULL << b2) > per_part && b2 < PP_L1_BITS + 10) ++b2;
-        const double avg = (double)nr / (double)(1ULL << b2);
-        const double round_cap = 0.7 * (double)pp_rc_records(S);
-        u32 sub = 0;
-        while (avg / (double)(1u << sub) > round_cap && sub < 5) ++sub;
-        // (a capacity hint asking for fewer partitions than this sizing — e.g. one group — keeps
-        // the slot-table kernel and its LDS overflow rounds)
-        if (avg <= per_part && avg / (double)(1u << sub) <= round_cap && B >= b2) {
-            B = b2;
-            k2 = B - PP_L1_BITS;
-            k3 = 0;
-            h->pp_rc_sub = std::max<u32>(sub, 1);  // >= 1 round bit: the flag doubles as "record-centric"
-        }
-    }
     // Compile-time specialised aggregation (result columns, raw records of a supported shape): a
     // partition is loaded once and aggregated in 2^sub LDS rounds, so partitions hold up to the
     // kernel's register budget of records and level 2 alone (<= 10 bits) sizes them — no level 3.
     h->pp_spec = -1;
     static const bool spec_on = !(X_ENV("DBG_X_PPSPEC") && X_ENV("DBG_X_PPSPEC")[0] == '0');
     u32 scap = 0, smax = 0;
-    const int shape = (spec_on && spec_ok && !h->pp_rc_sub && nsr == 0 && nr > 0) ? pp_spec_shape(S, &scap, &smax) : -1;
+    const int shape = (spec_on && spec_ok && nsr == 0 && nr > 0) ? pp_spec_shape(S, &scap, &smax) : -1;
     if (shape >= 0) {
         const double fill = 0.75 * (double)smax;  // average records per partition (the max stays below smax)
         u32 b2 = PP_L1_BITS + 1;
@@ -415,21 +392,12 @@ static int pp_agg(dbg_agg_handle* h, int mode, const OutDesc* od) {
     auto& T = h->ppk[1];
     // every final partition may spill (skewed keys): room for all their ids (<= 1 MB)
     const u32 SPILL_CAP = 1u << h->pp_bits;
-    if (h->pp_spec >= 0 || h->pp_rc_sub) {
+    if (h->pp_spec >= 0) {
         RETURN_IF(h->pp_spill.ensure(1 + (u64)SPILL_CAP));
         HIPCHECK(hipMemsetAsync(h->pp_spill, 0, 4, h->stream));
-    }
-    if (h->pp_spec >= 0) {
         prof::Scope ps("pp_agg", h->stream);
         launch_pp_agg_spec(h->stream, S, h->pp_spec, mode, 1u << h->pp_bits, R.part, R.fin, h->pp_spec_sub, o, h->pp_spill, SPILL_CAP);
         // partitions larger than its register budget (skewed keys): the generic kernel, spilled ids only
-        launch_pp_agg(h->stream, h->dspec, S, h->dbatches, mode, 1u << h->pp_bits, R.part, nullptr, R.fin, R.alt, nullptr, nullptr,
-                      o, h->pp_spill, SPILL_CAP);
-    } else if (h->pp_rc_sub) {
-        prof::Scope ps("pp_agg", h->stream);
-        launch_pp_agg_rc(h->stream, h->dspec, S, h->dbatches, mode, 1u << h->pp_bits, R.part, R.fin, 64 - h->pp_bits - h->pp_rc_sub,
-                         h->pp_rc_sub, o, h->pp_spill, SPILL_CAP);
-        // partitions too large for it (skewed keys): the slot-table kernel, over the spilled ids only
         launch_pp_agg(h->stream, h->dspec, S, h->dbatches, mode, 1u << h->pp_bits, R.part, nullptr, R.fin, R.alt, nullptr, nullptr,
                       o, h->pp_spill, SPILL_CAP);
     } else {

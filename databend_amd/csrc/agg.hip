@@ -956,8 +956,8 @@ __global__ void __launch_bounds__(STR1_NT) agg_insert_str1_kernel(const Spec* __
 // queue -> key offsets -> key bytes -> hash -> LDS probe -> the representative row's offsets ->
 // its bytes -> the arguments -> LDS atomics, seven dependent global round trips.  Here the rows
 // stay on their lanes (no queue): a row's key offsets and argument values are loaded together,
-// then its key bytes with the predicate's column (fetching a row ahead, SHORT_PIPE=1, costs two
-// waves per SIMD of occupancy and measured slower: C1 insert 0.26 -> 0.32 ms).  Each key of <= 7 bytes is packed with its length into
+// then its key bytes with the predicate's column (fetching a row ahead costs two waves per SIMD
+// of occupancy and measured slower: C1 insert 0.26 -> 0.32 ms).  Each key of <= 7 bytes is packed with its length into
 // one word, and the LDS probe compares the packed words against a side array beside the table —
 // the representative row is read only by the lane that claims a slot (for the group hash the HBM
 // entry needs).
@@ -973,9 +973,6 @@ __global__ void __launch_bounds__(STR1_NT) agg_insert_str1_kernel(const Spec* __
 // ------------------------------------------------------------------------------------------
 #define SHORT_MAXA 8
 #define SHORT_MAX_SLOTS 65536  // HBM table slots up to which the short-key insert is taken
-#ifndef SHORT_PIPE
-#define SHORT_PIPE 0
-#endif
 #define PK_NONE (~0ULL)
 #define PK_GEN (~0ULL - 1)
 typedef __attribute__((address_space(3))) u64 lds_u64;
@@ -986,142 +983,9 @@ struct ShortRow {
     u64 lo[SHORT_MAXA];     // argument low words (or the whole value)
     u64 hi[SHORT_MAXA];     // Decimal128 high words of wide sums
 };
-// End of the short-key insert: a merge tree over parked tables, fan-in SHORT_FANIN per level.
-// block_flush parks each workgroup's table and lets the last of every FLUSH_GROUP merge them and
-// flush to HBM, so G / FLUSH_GROUP leaders still add into the same few HBM slots, serialised at
-// the memory side (C1: 366 leaders x 4 groups).  Here a level's leader parks its merged table
-// again, one level up, until one root flushes: the HBM table sees one add per group.  Parked rows
-// carry the slot's packed keys (words n_words+1, n_words+2), so a merge compares them in LDS and
-// never reads a representative row.  Node n of level L parks in the scratch row of workgroup
-// n * FANIN^L (read by its own leader before), its tickets sit at a per-level offset.  Hand-off
-// as in block_flush: sc1 stores, vmcnt drain + barrier before the ticket add, acquire + sc1 loads.
-// A table with a generic slot or more than SCR_ENTRIES short slots flushes directly and parks an
-// empty row.
-#ifndef SHORT_FANIN_LOG
-#define SHORT_FANIN_LOG 2  // 4 parked tables per leader (16: 3 levels instead of 6 for C1, the same 0.274 ms step)
-#endif
-#define SHORT_FANIN (1u << SHORT_FANIN_LOG)
-__device__ __forceinline__ void short_tree_flush(const Spec& S, const BatchDesc* batches, const BatchDesc& B, u64* lds, u32 lds_slots,
-                                                 u32 sw, u32* lcount, u64* pk0, u64* pk1, const TableDesc& t, u32 my_claims) {
-    const u32 lmask = lds_slots - 1;
-    const u32 llimit = lds_slots - lds_slots / 4;
-    const u32 nw = (u32)S.n_words;
-    u64* counts = t.scratch;
-    u64* tickets = t.scratch + t.scr_blocks;
-    u64* rows = t.scratch + 2 * (u64)t.scr_blocks;
-    u32 node = blockIdx.x, n_nodes = gridDim.x, shift = 0, toff = 0;
-    for (;;) {
-        // the table in LDS: count slots; [4] generic slots, [5] short slots
-        if (threadIdx.x == 0) lcount[4] = lcount[5] = 0;
-        __syncthreads();
-        for (u32 s = threadIdx.x; s < lds_slots; s += BLOCK) {
-            const u64 e = lds[(u64)s * sw];
-            if (e == SLOT_EMPTY) continue;
-            atomicAdd(&lcount[pk0[s] == PK_GEN || pk0[s] == PK_NONE ? 4 : 5], 1u);
-        }
-        __syncthreads();
-        const bool root = n_nodes == 1;
-        const bool direct = root || lcount[4] != 0 || lcount[5] > SCR_ENTRIES;
-        const u64 b = (u64)node << shift;  // this node's scratch row
-        if (direct) {
-            flush_lds_direct<false, false, true, false>(S, batches, B, lds, lds_slots, sw, BLOCK, t, my_claims);
-            if (!root && threadIdx.x == 0) st_sc1(counts + b, 0);
-        } else {
-            if (threadIdx.x == 0) lcount[2] = 0;
-            __syncthreads();
-            u64* row = rows + b * SCR_ENTRIES * sw;
-            for (u32 s = threadIdx.x; s < lds_slots; s += BLOCK) {
-                const u64* p = lds + (u64)s * sw;
-                if (p[0] == SLOT_EMPTY) continue;
-                const u32 k = atomicAdd(&lcount[2], 1u);
-                u64* d = row + (u64)k * sw;
-                for (u32 w = 0; w <= nw; ++w) st_sc1(d + w, p[w]);
-                st_sc1(d + nw + 1, pk0[s]);
-                st_sc1(d + nw + 2, pk1[s]);
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) st_sc1(counts + b, lcount[2]);
-        }
-        if (root) break;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        const u32 g = node / SHORT_FANIN;
-        const u32 gsize = min((u32)SHORT_FANIN, n_nodes - g * SHORT_FANIN);
-        if (threadIdx.x == 0) {
-            const u64 tk = atomicAdd((unsigned long long*)(tickets + toff + g), 1ULL);
-            lcount[3] = tk == (u64)gsize - 1 ? 1u : 0u;
-        }
-        __syncthreads();
-        if (!lcount[3]) break;
-        // this workgroup leads node g one level up: merge the members' parked rows
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            tickets[toff + g] = 0;  // ready for the next launch (all members have added)
-        }
-        lds_table_init<false>(S, lds, lds_slots, sw, BLOCK);
-        for (u32 j = threadIdx.x; j < lds_slots; j += BLOCK) pk0[j] = pk1[j] = PK_NONE;
-        if (threadIdx.x == 0) lcount[0] = 0;
-        __syncthreads();
-        for (u32 f = threadIdx.x; f < gsize * SCR_ENTRIES; f += BLOCK) {
-            const u64 mb = ((u64)g * SHORT_FANIN + f / SCR_ENTRIES) << shift, k = f % SCR_ENTRIES;
-            const u64* r = rows + (mb * SCR_ENTRIES + k) * sw;
-            const u64 cnt = ld_sc1(counts + mb);
-            const u64 e = ld_sc1(r);
-            if (k >= cnt) continue;
-            const u64 q0 = ld_sc1(r + nw + 1), q1 = ld_sc1(r + nw + 2);
-            u32 pos = (u32)slot_mix(q0 ^ slot_mix(q1)) & lmask;
-            int ls = -1;
-            for (int p = 0; p < LDS_PROBE_CAP; ++p) {
-                wptr<AS_LDS> ep = asp<AS_LDS>(lds + (u64)pos * sw);
-                u64 ev = vld<AS_LDS>(ep);
-                if (ev == SLOT_EMPTY) {
-                    if (*(vlds_u32*)lcount >= llimit) break;
-                    const u64 old = at_cas<AS_LDS>(ep, SLOT_EMPTY, e);
-                    if (old == SLOT_EMPTY) {
-                        ((vlds_u64*)pk0)[pos] = q0;
-                        ((vlds_u64*)pk1)[pos] = q1;
-                        __hip_atomic_fetch_add((__attribute__((address_space(3))) u32*)lcount, 1u, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_WORKGROUP);
-                        ls = (int)pos;
-                        break;
-                    }
-                }
-                if (((vlds_u64*)pk0)[pos] == q0 && ((vlds_u64*)pk1)[pos] == q1) {
-                    ls = (int)pos;
-                    break;
-                }
-                pos = (pos + 1) & lmask;
-            }
-            if (ls >= 0) {
-                apply_state<AS_LDS, true, AS_GLB, true, false>(S, asp<AS_LDS>(lds + (u64)ls * sw), r, batches);
-                continue;
-            }
-            // the merge table is full: this row goes to HBM by itself
-            bool claimed;
-            const u64 h = group_hash(B.keys, S.n_keys, ref_row(e));
-            const u64 gs = g_find<false>(S, batches, B.keys, ref_row(e), e, h, t, t.probe_limit, claimed);
-            if (gs == ~0ULL) {
-                push_ovf_rec<true>(S, t, e, r);
-                continue;
-            }
-            my_claims += claimed ? 1 : 0;
-            apply_state<AS_GLB, true, AS_GLB, true, false>(S, asp<AS_GLB>(t.slots + gs * t.stride_words), r, batches);
-        }
-        __syncthreads();
-        toff += (n_nodes + SHORT_FANIN - 1) / SHORT_FANIN;
-        node = g;
-        n_nodes = (n_nodes + SHORT_FANIN - 1) / SHORT_FANIN;
-        shift += SHORT_FANIN_LOG;
-    }
-    if (my_claims) atomicAdd(&lcount[1], my_claims);
-    __syncthreads();
-    if (threadIdx.x == 0 && lcount[1]) atomicAdd((unsigned long long*)(t.counters + CNT_CLAIMS), (unsigned long long)lcount[1]);
-}
-
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6))) agg_insert_short_kernel(const Spec* __restrict__ spec, const BatchDesc* __restrict__ batches,
                                                                 u32 bid, u64 rows, u64 rows_per_block, TableDesc t, u32 lds_slots,
-                                                                u32 rep_mask, int xmode, u32 narrow, int tree_ok, u64* trace) {
+                                                                u32 rep_mask, int xmode, u32 narrow, u64* trace) {
     extern __shared__ __attribute__((aligned(16))) u64 lds[];
     // EXPERIMENT (TRACE=1 builds, DBG_X_TRACE_SHORT): [0] first workgroup start, [1] / [2] first /
     // last row loop end, [3] last flush start, [4] last workgroup end (s_memrealtime, 100 MHz)
@@ -1136,7 +1000,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6)))
     const Spec& S = *spec;
     const BatchDesc& B = batches[bid];
     const u32 sw = S.stride_words;
-    u32* lcount = (u32*)(lds + (u64)lds_slots * sw);  // [0] lds claims, [1] hbm claims, [2..5] flush
+    u32* lcount = (u32*)(lds + (u64)lds_slots * sw);  // [0] lds claims, [1] hbm claims, [2..3] flush
     u64* pk0 = lds + (u64)lds_slots * sw + 4;          // packed keys of short slots (PK_NONE / PK_GEN)
     u64* pk1 = pk0 + lds_slots;
     const u32 lmask = lds_slots - 1;
@@ -1291,24 +1155,10 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6)))
             if (A.kind == DBG_AGG_AVG) at_add<AS_LDS>(w + (A.sumk == SUMK_I128 ? 2 : 1), 1ULL);
         }
     };
-    static_assert(SHORT_PIPE == 0 || SHORT_PIPE == 1, "");
-    u64 i = r0 + threadIdx.x;
-    if (SHORT_PIPE && i < r1) {  // loads one row ahead (measured slower: occupancy 6 -> 4 waves)
+    for (u64 i = r0 + threadIdx.x; i < r1; i += BLOCK) {
         ShortRow cur;
         fetch(i, cur);
-        for (; i < r1; i += BLOCK) {
-            ShortRow nxt;
-            const u64 in = i + BLOCK;
-            if (in < r1) fetch(in, nxt);
-            process(i, cur);
-            cur = nxt;
-        }
-    } else {
-        for (; i < r1; i += BLOCK) {
-            ShortRow cur;
-            fetch(i, cur);
-            process(i, cur);
-        }
+        process(i, cur);
     }
     __syncthreads();
     tmark(1, false);
@@ -1324,10 +1174,8 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(6)))
         }
         __syncthreads();
     }
-    const bool tree = tree_ok && t.scratch != nullptr && gridDim.x > 1 && gridDim.x <= t.scr_blocks;  // uniform
     tmark(3, true);
-    if (tree) short_tree_flush(S, batches, B, lds, lds_slots, sw, lcount, pk0, pk1, t, my_claims);
-    else block_flush<false, false, true, false>(S, batches, B, lds, lds_slots, sw, lcount, BLOCK, t, my_claims);
+    block_flush<false, false, true, false>(S, batches, B, lds, lds_slots, sw, lcount, BLOCK, t, my_claims);
     tmark(4, true);
 }
 
@@ -2212,7 +2060,6 @@ __device__ __forceinline__ void fused_dense(const Spec& S, const BatchDesc* batc
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         atomicExch((unsigned long long*)(t.counters + CNT_FIN_TICKET), 0ULL);
-        atomicExch((unsigned long long*)(t.counters + CNT_TAIL), 0ULL);  // every workgroup has left its tail
         bad = 0;
         vcl = 0;
         lcount[2] = 0;
@@ -2405,7 +2252,6 @@ __device__ __forceinline__ void fused_chain(const Spec& S, const BatchDesc* batc
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         atomicExch((unsigned long long*)(t.counters + CNT_FIN_TICKET), 0ULL);
-        atomicExch((unsigned long long*)(t.counters + CNT_TAIL), 0ULL);  // every workgroup has left its tail
         bad = 0;
         vcl = 0;
         if (kPhaseTrace && ff.trace) ff.trace[4] = __builtin_amdgcn_s_memrealtime();
@@ -2738,7 +2584,6 @@ __device__ __forceinline__ void fused_chain_tagged(const Spec& S, const BatchDes
     //    group of the launch that is not in the HBM table
     if (threadIdx.x == 0) {
         atomicExch((unsigned long long*)(t.counters + CNT_FIN_TICKET), 0ULL);
-        atomicExch((unsigned long long*)(t.counters + CNT_TAIL), 0ULL);
         if (kPhaseTrace && ff.trace) ff.trace[4] = __builtin_amdgcn_s_memrealtime();
     }
     if (flushed) empty_own();
@@ -2827,11 +2672,6 @@ __device__ __forceinline__ void fused_chain_tagged(const Spec& S, const BatchDes
 // of two in flight keep each wave's window of the column to 2 x 2 grid strides
 #define FAST_UNROLL 2
 #endif
-#ifndef TAIL_ON
-// dynamic stream tail of fused-chain launches: measured and not kept (C2 step 45.7 -> 51.3 us,
-// profiles/r04/c2_tail_ab.json); make TAIL=1 builds it for A/B runs
-#define TAIL_ON 0
-#endif
 typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 // Column data reached through a descriptor is a generic pointer to the compiler, which then
 // emits flat loads: those count against lgkmcnt too and retire out of order, so every LDS wait
@@ -2907,19 +2747,6 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
     u64 k = (u64)blockIdx.x * NT + threadIdx.x;
     const u64 step = (u64)FAST_UNROLL * gstride;
     const u64 lastv = nvec ? nvec - 1 : 0;
-    // Dynamic tail (fused-chain launches): the grid-strided static part covers ~80 % of the
-    // vectors in whole rounds of the grid; the rest is cut into chunks of NT x FAST_UNROLL vectors
-    // that workgroups done with their static share take from a device counter — so the chip's
-    // fast CUs absorb the end of the stream instead of waiting for its slow ones (workgroups
-    // finished streaming between 27.8 and 35.0 us of a C2 launch).  The counter
-    // (CNT_TAIL) is reset by the launch's last group leader.
-    constexpr u64 TAIL_CH = (u64)NT * FAST_UNROLL;
-    const bool dyn = TAIL_ON && ff.on && t.scratch != nullptr && gridDim.x > 1 && gridDim.x <= t.scr_blocks;
-    u64 nstat = nvec, nch = 0;
-    if (dyn) {
-        nstat = ((nvec * 4 / 5) / step) * step;
-        nch = (nvec - nstat + TAIL_CH - 1) / TAIL_CH;
-    }
     // The first round's loads go out before the LDS table is initialised: they need nothing but
     // the kernel arguments, and the barrier below waits for LDS only, so they stay in flight
     // across the initialisation (one memory trip earlier on every CU's hand-over between launches).
@@ -2927,7 +2754,7 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
 #pragma unroll
     for (int u = 0; u < FAST_UNROLL; ++u) {
         u64 idx = k + u * gstride;
-        y[u] = __builtin_nontemporal_load(vp + (idx < nstat ? idx : lastv));
+        y[u] = __builtin_nontemporal_load(vp + (idx < nvec ? idx : lastv));
     }
     lds_table_init<false>(S, lds, lds_slots, sw, NT);
     if (threadIdx.x < 4) lcount[threadIdx.x] = 0;
@@ -3126,81 +2953,31 @@ __global__ void __launch_bounds__(NT) agg_insert_fast_kernel(const Spec* __restr
         }
     };
 
-    u64 tail_grab = 0;  // thread 0: the first tail chunk, taken now (its latency hides behind the stream)
-    if (dyn && nch && threadIdx.x == 0) tail_grab = atomicAdd((unsigned long long*)(t.counters + CNT_TAIL), 1ULL);
     // Software pipeline: the next round's FAST_UNROLL loads are issued before this round is
     // filtered and queued (the first round's went out before the table's initialisation), so a
     // wave busy with its ballots and LDS queue writes still has 64 B/lane in flight (without it
     // the per-round processing sits on the load critical path).  The loop condition is
     // wave-uniform (ballot) because the queue needs all 64 lanes.
-    while (__ballot(k < nstat) != 0) {
+    while (__ballot(k < nvec) != 0) {
         const u64 kn = k + step;
         v4u yn[FAST_UNROLL];
 #pragma unroll
         for (int u = 0; u < FAST_UNROLL; ++u) {
             u64 idx = kn + u * gstride;
-            yn[u] = __builtin_nontemporal_load(vp + (idx < nstat ? idx : lastv));
+            yn[u] = __builtin_nontemporal_load(vp + (idx < nvec ? idx : lastv));
         }
         u64 bases[FAST_UNROLL];
         u32 actm = 0;
 #pragma unroll
         for (int u = 0; u < FAST_UNROLL; ++u) {
             u64 idx = k + u * gstride;
-            actm |= (idx < nstat ? 1u : 0u) << u;
+            actm |= (idx < nvec ? 1u : 0u) << u;
             bases[u] = idx * V;
         }
         handle_group(y, bases, FAST_UNROLL, actm);
 #pragma unroll
         for (int u = 0; u < FAST_UNROLL; ++u) y[u] = yn[u];
         k = kn;
-    }
-    if (dyn && nch) {
-        // chunk ids pass through LDS behind a bare s_barrier (no fence: the loads in flight are
-        // not drained); the next chunk's loads are issued, and the chunk after it taken, before
-        // the current chunk is filtered
-        __shared__ u32 tail_id[2];
-        auto load_chunk = [&](u32 c, v4u* yy) {
-#pragma unroll
-            for (int u = 0; u < FAST_UNROLL; ++u) {
-                const u64 idx = nstat + (u64)c * TAIL_CH + (u64)u * NT + threadIdx.x;
-                yy[u] = __builtin_nontemporal_load(vp + (idx < nvec ? idx : lastv));
-            }
-        };
-        auto publish = [&](u32 slot, u64 v) -> u32 {
-            if (threadIdx.x == 0) tail_id[slot] = (u32)min<u64>(v, nch);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            return tail_id[slot];
-        };
-        u32 par = 0;
-        u32 cur = publish(par, tail_grab);
-        par ^= 1;
-        v4u yc[FAST_UNROLL];
-        if (cur < nch) {
-            load_chunk(cur, yc);
-            if (threadIdx.x == 0) tail_grab = atomicAdd((unsigned long long*)(t.counters + CNT_TAIL), 1ULL);
-        }
-        while (cur < nch) {
-            const u32 nxt = publish(par, tail_grab);
-            par ^= 1;
-            v4u yn[FAST_UNROLL];
-            if (nxt < nch) {
-                load_chunk(nxt, yn);
-                if (threadIdx.x == 0) tail_grab = atomicAdd((unsigned long long*)(t.counters + CNT_TAIL), 1ULL);
-            }
-            u64 bases[FAST_UNROLL];
-            u32 actm = 0;
-#pragma unroll
-            for (int u = 0; u < FAST_UNROLL; ++u) {
-                const u64 idx = nstat + (u64)cur * TAIL_CH + (u64)u * NT + threadIdx.x;
-                actm |= (idx < nvec ? 1u : 0u) << u;
-                bases[u] = idx * V;
-            }
-            handle_group(yc, bases, FAST_UNROLL, actm);
-#pragma unroll
-            for (int u = 0; u < FAST_UNROLL; ++u) yc[u] = yn[u];
-            cur = nxt;
-        }
     }
     if (PRED && vqn) {
         __builtin_amdgcn_wave_barrier();
@@ -3341,6 +3118,41 @@ bool insert_can_fuse(const Spec& S, const BatchDesc& hb, u64 cap) {
            (cap + 1) * S.stride_words * 8 <= fast_shmem(fast_table_bytes(S));
 }
 
+// EXPERIMENT (TRACE=1 builds, DBG_X_TRACE_SHORT): the phase-trace ring of the short-key insert, 8
+// words per launch and 4096 launches, its medians dumped at exit.  Returns this launch's entry,
+// initialised on `s` (nullptr: tracing is off).
+static u64* exp_short_trace(hipStream_t s) {
+    if (!(kPhaseTrace && X_ENV("DBG_X_TRACE_SHORT"))) return nullptr;
+    static u64* buf = nullptr;
+    static u32 launch = 0;
+    static const u64 init[8] = {~0ULL, ~0ULL, 0, 0, 0, 0, 0, 0};
+    if (!buf) {
+        if (hipMalloc((void**)&buf, 4096 * 64) != hipSuccess) buf = nullptr;
+        if (buf) hipMemset(buf, 0, 4096 * 64);
+        atexit([] {
+            std::vector<u64> hb(4096 * 8);
+            (void)hipDeviceSynchronize();
+            (void)hipMemcpy(hb.data(), buf, hb.size() * 8, hipMemcpyDeviceToHost);
+            std::vector<std::vector<double>> d(4);
+            for (int k = 0; k < 4096; ++k) {
+                const u64* r = &hb[k * 8];
+                if (r[0] == 0 || r[0] == ~0ULL || r[4] == 0) continue;
+                for (int p = 1; p <= 4; ++p) d[p - 1].push_back((double)(r[p] - r[0]) * 0.01);
+            }
+            const char* nm[] = {"first row loop end", "last row loop end", "last flush start", "last workgroup end"};
+            for (int p = 0; p < 4; ++p) {
+                if (d[p].empty()) continue;
+                std::sort(d[p].begin(), d[p].end());
+                fprintf(stderr, "short trace %-20s median %7.2f us  (n=%zu)\n", nm[p], d[p][d[p].size() / 2], d[p].size());
+            }
+        });
+    }
+    if (!buf) return nullptr;
+    u64* x_tr = buf + (u64)(launch++ & 4095) * 8;
+    (void)hipMemcpyAsync(x_tr, init, sizeof(init), hipMemcpyHostToDevice, s);
+    return x_tr;
+}
+
 InsertPath launch_insert(hipStream_t s, const Spec* dspec, const Spec& S, const BatchDesc* batches, u32 bid, u64 rows, bool records,
                          const TableDesc& t, bool use_lds, const BatchDesc* hb, const FusedFin* fused) {
     if (rows == 0) return INS_NONE;
@@ -3409,40 +3221,8 @@ InsertPath launch_insert(hipStream_t s, const Spec* dspec, const Spec& S, const 
         }
         static const bool x_wide = X_ENV("DBG_X_NARROW") && X_ENV("DBG_X_NARROW")[0] == '0';
         if (x_wide) narrow = 0;
-        static const bool x_tree = X_ENV("DBG_X_TREE") && X_ENV("DBG_X_TREE")[0] == '1';
-        u64* x_tr = nullptr;
-        if (kPhaseTrace && X_ENV("DBG_X_TRACE_SHORT")) {  // EXPERIMENT: 8 words per launch, 4096 launches
-            static u64* buf = nullptr;
-            static u32 launch = 0;
-            static const u64 init[8] = {~0ULL, ~0ULL, 0, 0, 0, 0, 0, 0};
-            if (!buf) {
-                if (hipMalloc((void**)&buf, 4096 * 64) != hipSuccess) buf = nullptr;
-                if (buf) hipMemset(buf, 0, 4096 * 64);
-                atexit([] {
-                    std::vector<u64> hb(4096 * 8);
-                    (void)hipDeviceSynchronize();
-                    (void)hipMemcpy(hb.data(), buf, hb.size() * 8, hipMemcpyDeviceToHost);
-                    std::vector<std::vector<double>> d(4);
-                    for (int k = 0; k < 4096; ++k) {
-                        const u64* r = &hb[k * 8];
-                        if (r[0] == 0 || r[0] == ~0ULL || r[4] == 0) continue;
-                        for (int p = 1; p <= 4; ++p) d[p - 1].push_back((double)(r[p] - r[0]) * 0.01);
-                    }
-                    const char* nm[] = {"first row loop end", "last row loop end", "last flush start", "last workgroup end"};
-                    for (int p = 0; p < 4; ++p) {
-                        if (d[p].empty()) continue;
-                        std::sort(d[p].begin(), d[p].end());
-                        fprintf(stderr, "short trace %-20s median %7.2f us  (n=%zu)\n", nm[p], d[p][d[p].size() / 2], d[p].size());
-                    }
-                });
-            }
-            if (buf) {
-                x_tr = buf + (u64)(launch++ & 4095) * 8;
-                (void)hipMemcpyAsync(x_tr, init, sizeof(init), hipMemcpyHostToDevice, s);
-            }
-        }
         hipLaunchKernelGGL(agg_insert_short_kernel, dim3((u32)blocks), dim3(BLOCK), shmem, s, dspec, batches, bid, rows, rpb, t, lslots,
-                           x_rep ? x_rep - 1 : 0u, x_short, narrow, x_tree && S.stride_words >= S.n_words + 3 ? 1 : 0, x_tr);
+                           x_rep ? x_rep - 1 : 0u, x_short, narrow, exp_short_trace(s));
         return INS_SHORT;
     }
     // enough workgroups to fill 256 CUs several times over, each a contiguous row range

@@ -402,10 +402,9 @@ int dbg_agg_get_strategy(dbg_agg_handle* h, int* partitioned, uint64_t* extra_ro
 /* Read-only statistics of the last partitioned finalize (either pointer may be NULL).
  * *final_bits = the number of hash bits that select a final partition: a record's final partition
  * is the top *final_bits bits of its group hash (0 before the first partitioned finalize).
- * *spilled_partitions = the final partitions that the specialised or record-centric aggregation
- * found larger than its per-partition record budget and handed to the generic kernel (0 when
- * neither ran).  Both are read from what the finalize already copied to the host: the call never
- * touches the device. */
+ * *spilled_partitions = the final partitions that the specialised aggregation found larger than
+ * its per-partition record budget and handed to the generic kernel (0 when it did not run).  Both
+ * are read from what the finalize already copied to the host: the call never touches the device. */
 int dbg_agg_get_pp_stats(dbg_agg_handle* h, uint32_t* final_bits, uint64_t* spilled_partitions);
 /* Which insert kernel the handle's work took, cumulative since dbg_agg_create (a reset keeps
  * the counts): counts[i] = launches of variant i, for i < n; entries past DBG_INSERT_N_PATHS are

@@ -26,7 +26,7 @@ import pytest
 from databend_amd import column as col
 from databend_amd.column import Column
 from databend_amd.ffi import check, lib
-from tests.test_gpu_fused_dense import FusedRunner
+from tests.test_gpu_fused_count_small_keys import FusedRunner
 
 pytestmark = pytest.mark.gpu
 

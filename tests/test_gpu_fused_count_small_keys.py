@@ -1,10 +1,11 @@
 """The fused insert + finalize launch for COUNT(*) over a <= 16-bit key (ClickBench Q8 shape) and its
-direct-mapped hand-off (agg.hip fused_dense): every workgroup adds its LDS counts into a dense
-array indexed by the key, the last one finalizes from it.  Against the oracle: Int8 / UInt8 /
-Int16 / UInt16 keys with negative values and full ranges, several predicates, consecutive steps
-on one recycled table (the dense arrays must be clean again after every launch), a key count
-larger than the table's view (overflow records, the host's grow-and-finalize-again protocol),
-and the parked-row chain (DBG_X_DENSE=0 semantics: a table that is not empty at launch start)."""
+parked-row hand-offs (agg.hip fused_chain_tagged, and fused_chain where the tagged chain
+does not apply): every workgroup parks its LDS counts, group leaders merge them, the last leader
+finalizes.  Against the oracle: Int8 / UInt8 / Int16 / UInt16 keys with negative values and full
+ranges, several predicates, consecutive steps on one recycled table (the scratch rows of one
+launch must never validate in the next), a key count larger than the table's view (overflow
+records, the host's grow-and-finalize-again protocol), and a table that is not empty at launch
+start."""
 import ctypes as C
 
 import numpy as np
@@ -76,7 +77,7 @@ KEYS = [(col.Int8, -128, 128), (col.UInt8, 0, 256), (col.Int16, -32768, 32768), 
 
 
 @pytest.mark.parametrize("t,lo,hi", KEYS, ids=lambda x: repr(x))
-def test_fused_dense_matches_oracle(t, lo, hi):
+def test_fused_count_matches_oracle(t, lo, hi):
     rng = np.random.default_rng(abs(hash(repr(t))) % 2**32)
     r = FusedRunner(t)
     try:
@@ -95,10 +96,10 @@ def test_fused_dense_matches_oracle(t, lo, hi):
         r.close()
 
 
-def test_fused_dense_many_keys_overflow_view():
+def test_fused_count_many_keys_overflow_view():
     """30,000 distinct Int16 keys into a table sized for ~1,000: keys the LDS view cannot place
     become overflow records; the host grows the table and finalizes again — exact counts, and
-    the next step on the same table is exact too (dense arrays cleaned)."""
+    the next step on the same table is exact too."""
     rng = np.random.default_rng(5)
     r = FusedRunner(col.Int16)
     try:

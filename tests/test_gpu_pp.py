@@ -225,10 +225,11 @@ def test_pp_auto_probe_selects_partitioned_for_c4():
 
 @pytest.mark.parametrize("kind", ["i64", "i64_i32", "dup_heavy", "skewed"])
 def test_pp_record_centric(kind):
-    """Record-centric aggregation of raw records (pp.hip pp_agg_rc_kernel): level-2 partitions of
-    ~PP_RC_PART records aggregated in LDS rounds.  Mostly-unique keys (its target), keys with a few
-    records each, and a skewed key holding a large share of the rows — whose partition exceeds one
-    round's LDS and is spilled to the slot-table kernel — all against the oracle."""
+    """The shapes the record-centric aggregation was written for (that kernel was opt-in in
+    experiment builds only and has been removed; the shipped library always took the slot-table
+    kernels of pp.hip here, and still does).  Mostly-unique keys, keys with a few records each, and
+    a skewed key holding a large share of the rows — whose partition exceeds one kernel's budget
+    and is spilled to the generic slot-table kernel — all against the oracle."""
     rng = np.random.default_rng(len(kind))
     n = 6_000_000
     if kind == "i64":
