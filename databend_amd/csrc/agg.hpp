@@ -87,7 +87,7 @@ struct TableDesc {
     u64* ovf_recs;  // [keyref][words...] per record, stride = stride_words
     u64 ovf_recs_cap;
     // per-workgroup parking rows of small LDS tables (merged by the last workgroup of each group,
-    // see block_flush in agg.hip): [count u64 x scr_blocks][group tickets u64 x scr_blocks / 2]
+    // see block_flush in agg_table.hpp): [count u64 x scr_blocks][group tickets u64 x scr_blocks / 2]
     // [group meta u64 x scr_blocks / 2][scr_blocks x SCR_ENTRIES x stride_words]
     // [scr_blocks / SCR_GROUP group rows x SCR_ENTRIES x stride_words] (fused chain)
     u64* scratch;
@@ -103,7 +103,7 @@ struct TableDesc {
 inline size_t scr_words(u32 blocks, u32 stride_words) {
     return (size_t)blocks * (2 + (size_t)SCR_ENTRIES * stride_words) + (size_t)(blocks / SCR_GROUP) * SCR_ENTRIES * stride_words;
 }
-// launches between two wraps of the tagged fused chain's narrower tag (agg.hip, TAG2_BITS): the
+// launches between two wraps of the tagged fused chain's narrower tag (agg_chain.hpp, TAG2_BITS): the
 // host keeps sequence numbers off its multiples and clears the scratch at each (fin_launch)
 #define FIN_SEQ_TAG_PERIOD (1ULL << 20)
 #define DBG_INSERT_MAX_BLOCKS 2048  // grid cap of every insert launch (scratch rows are sized by it)
@@ -112,7 +112,7 @@ enum { CNT_CLAIMS = 0, CNT_OVF_ROWS = 1, CNT_OVF_RECS = 2, CNT_ERR = 3, CNT_FIX_
        CNT_WORDS = 8 };  // word 7 is reserved: the counter block and the host mirror built on CNT_WORDS keep their layout
 enum { ERR_DEC_OVERFLOW = 1, ERR_OVF_LOST = 2, ERR_FIXED_INCOMPLETE = 4, ERR_MINMAX_SPIN = 8, ERR_CHAIN_SPIN = 16 };
 
-// ---- device helpers shared by agg.hip and part.hip ----
+// ---- device helpers shared by the agg*.hip units and part.hip ----
 // Slot placement for inline keys: any good mixer works (placement is not observable); the
 // reference hash is recomputed from the key wherever routing needs it.  A bijection of u64
 // (xor-shift by 32 and odd multipliers are invertible), so part.hip can sort mixed keys and
@@ -135,7 +135,7 @@ __host__ __device__ __forceinline__ u64 slot_unmix(u64 y) {
 static_assert(0xd6e8feb86659fd93ULL * mul_inverse_u64(0xd6e8feb86659fd93ULL) == 1, "inverse");
 
 // State updates on an LDS (AS_LDS) or HBM (AS_GLB) slot; the address space is a template
-// parameter (see agg.hip: a generic pointer compiles to FLAT atomics).
+// parameter (see agg_dev.hpp: a generic pointer compiles to FLAT atomics).
 #define AS_GLB 1
 #define AS_LDS 3
 template <int AS> using wptr = __attribute__((address_space(AS))) u64*;
@@ -238,7 +238,7 @@ constexpr bool kExperiments = false;
 #endif
 
 struct FusedFin;
-// ---- launch wrappers (agg.hip) ----
+// ---- launch wrappers, by unit (agg_table.hpp has the map of the agg*.hip units) ----
 // part.hip: radix-partitioned COUNT(*) insert for high-cardinality single integer keys
 u32 part_slice_bits(const Spec& S, const BatchDesc& hb, u64 rows, u64 cap);  // 0 = not eligible
 size_t part_temp_bytes(int width, u64 rows, u32 sb, u64 cap);
@@ -251,6 +251,7 @@ hipError_t launch_part_slices(hipStream_t s, const TableDesc& t, u32 sb, const u
 u64 part_direct_status_words(u64 cap, u32 sb);
 hipError_t launch_part_direct(hipStream_t s, const TableDesc& t, u32 sb, const u64* sorted, const u64* bounds, u64* status, int key_width,
                               void* out_key, u64* out_cnt, u64 cap_groups, u64* totals);
+// agg.hip
 void launch_table_init(hipStream_t s, const Spec* dspec, const Spec& hspec, u64* slots, u64 cap, u64* zero_counters = nullptr);
 // the insert kernel a launch_insert call took (dbg_agg_insert_paths counts them per handle, in
 // this order); INS_NONE: no rows, nothing launched
@@ -278,6 +279,9 @@ void launch_retry(hipStream_t s, const Spec* dspec, const Spec& hspec, const Bat
                   u64 n_rows, u64 n_recs, const u64* rows_list, const u64* recs_list);
 void launch_rehash(hipStream_t s, const Spec* dspec, const Spec& hspec, const BatchDesc* batches, const u64* old_slots,
                    u64 old_cap, const TableDesc& t);
+// host side: would launch_insert of this batch take the fast kernel (and so could fuse)?
+bool insert_can_fuse(const Spec& S, const BatchDesc& hb, u64 cap);
+// agg_finalize.hip
 // finalize: counts per block of occupied slots (and string bytes per key col); returns blocks used
 u64 finalize_blocks(u64 cap);
 // scheme 0: hash % n; 1: radix bits [48 - r, 48); 2: lpart[slot] (legacy buckets, launch_legacy_slot_bucket)
@@ -320,7 +324,10 @@ void launch_finalize_small(hipStream_t s, const Spec* dspec, const BatchDesc* ba
                            u64* totals, u64* host_mirror /* mapped pinned: counters, totals, recycled, seq */,
                            int recycle, u64 seq);
 void launch_finish_outputs(hipStream_t s, const OutDesc& out, const u64* totals, int n_keys, int n_aggs);
-void launch_ser_compact(hipStream_t s, const u8* lens, const u8* src, u32 stride, u64 n, u64* offs, u8* dst, u64* total);
+void launch_write_results(hipStream_t s, const Spec* dspec, const Spec& hspec, const BatchDesc* batches, const TableDesc& t,
+                          const u64* pos /* scanned hist */, const u64* str_pos, const OutDesc& out);
+void launch_pack_bits(hipStream_t s, const u8* bytes, u64 n, u8* bits);
+// agg.hip: the fused finalize
 // finalize_small fused into the fast insert: the last workgroup to finish runs it (one launch per
 // batch).  Tables of at most FUSED_FIN_SLOTS slots whose copy fits the insert's LDS.
 #define FUSED_FIN_SLOTS 2048
@@ -343,11 +350,8 @@ struct FusedFin {
     u64* dense;
     u32 dense_n;
 };
-// host side: would launch_insert of this batch take the fast kernel (and so could fuse)?
-bool insert_can_fuse(const Spec& S, const BatchDesc& hb, u64 cap);
-void launch_write_results(hipStream_t s, const Spec* dspec, const Spec& hspec, const BatchDesc* batches, const TableDesc& t,
-                          const u64* pos /* scanned hist */, const u64* str_pos, const OutDesc& out);
-void launch_pack_bits(hipStream_t s, const u8* bytes, u64 n, u8* bits);
+// agg_export.hip
+void launch_ser_compact(hipStream_t s, const u8* lens, const u8* src, u32 stride, u64 n, u64* offs, u8* dst, u64* total);
 // String MIN/MAX (MMK_STR) results.  totals[a] (n_aggs words, zeroed) += payload bytes of String
 // aggregate a over the table's groups.
 void launch_str_agg_bytes(hipStream_t s, const Spec* dspec, const BatchDesc* batches, const TableDesc& t, u64* totals);

@@ -1,4 +1,4 @@
-// agg_dev.hpp — device helpers shared by agg.hip (HBM table) and pp.hip (partitioned payload):
+// agg_dev.hpp — device helpers shared by the agg*.hip units (HBM table) and pp.hip (partitioned payload):
 // packed-key hashing, state updates (accumulate_keys / merge_states) and results (merge_result).
 #pragma once
 #include "agg.hpp"

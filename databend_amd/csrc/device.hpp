@@ -1,6 +1,6 @@
 // device.hpp — device-side building blocks of the gfx950 GROUP BY path.
 //
-// Shared by agg.hip / filter.hip (device) and abi.hip (host, to fill the descriptors).
+// Shared by the agg*.hip units / filter.hip (device) and abi.hip (host, to fill the descriptors).
 //  * DCol: a column as the kernels see it — Databend's arrow layout (EXP/values.rs:157-176) or a
 //    strided view into a partial-state record buffer.
 //  * the group-hash family of EAGG/group_hash.rs:39-265, bit-exact (partition routing depends on it)

@@ -2835,7 +2835,7 @@ __global__ void __launch_bounds__(PP_GNT) pp_grec_export_kernel(const Spec* __re
 }
 
 // Legacy bucket of every group record (enable_experimental_aggregate_hashtable = 0), as
-// agg.hip legacy_slot_bucket_kernel does for the HBM table's slots.
+// agg_finalize.hip legacy_slot_bucket_kernel does for the HBM table's slots.
 __global__ void __launch_bounds__(PP_GNT) pp_grec_legacy_bucket_kernel(const Spec* __restrict__ spec, const BatchDesc* __restrict__ batches,
                                                                       const u8* __restrict__ grec, u64 n, LegacyLayout L,
                                                                       u32* __restrict__ out) {
