@@ -10,8 +10,9 @@
 //                page is decoded where it lies in the chunk, page_base).  The
 //                element stream is parsed by the whole wave in lockstep (uniform loads, no lane
 //                divergence); literals and back-references are copied 64 bytes per step, and
-//                back-references read a 64 KiB LDS ring of the page's recent output (both formats
-//                reference at most 64 KiB back — an offset beyond the ring is a decode error).
+//                back-references read a 32 KiB LDS ring of the page's recent output (both formats
+//                reference at most 64 KiB back — an offset beyond the ring reads the page's own
+//                output in HBM).
 //   pq_walk      one lane per BYTE_ARRAY page: the value starts of PLAIN byte arrays (u32 length
 //                prefixes) — a dependent chain inside a page, parallel across pages.
 //   pq_decode    one workgroup per data page: definition levels and dictionary indices through

@@ -214,11 +214,33 @@ def test_string_dict_nested(dec, nested):
 @pytest.mark.parametrize("codec", [nat.LZ4, nat.SNAPPY, nat.ZSTD])
 def test_long_back_references(dec, codec):
     """a 40000-byte value repeated: the compressors emit one match of ~120 KB at offset 40000 —
-    longer than the offset, which is more than half the inflate's 64 KB history ring (LZ4 / Snappy)
-    and more than the Zstd ring (read from the output)."""
+    longer than the offset, which is more than the inflate's 32 KiB history ring (LZ4 / Snappy) and
+    more than the Zstd ring: both read it from the output."""
     rng = np.random.default_rng(8)
     x = bytes(rng.integers(0, 256, 40000, dtype=np.uint8))
     check_str(dec, [x, x, x, x, b"tail"], codecs=[codec])
+
+
+def test_zstd_ring_segments_and_far_overlap(dec):
+    """The native launch site of the Zstd kernel on both match paths: a String payload of zero
+    bytes and a period of 3 (ring matches of several 16 KiB segments) and a 10 000-byte value six
+    times (one overlapping match read from the output), as the frame walker classifies what the
+    writer's libzstd emits for it."""
+    import struct
+    from collections import Counter
+
+    from tests import zstd_frames as zf
+    x = bytes(np.random.default_rng(9).integers(0, 256, 10_000, dtype=np.uint8))
+    v = [bytes(100_000), b"abc" * 30_000, x * 6, b"tail"]
+    buf, _, _ = nat.write_column(v, "str", 0, None, False, codecs=[nat.ZSTD])
+    feats, at = Counter(), buf.find(b"\x28\xb5\x2f\xfd")
+    while at >= 0:
+        codec, ln, _ = struct.unpack_from("<BII", buf, at - 9)
+        assert codec == nat.ZSTD
+        feats.update(zf.inspect(buf[at:at + ln])[0])
+        at = buf.find(b"\x28\xb5\x2f\xfd", at + ln)
+    assert feats["ring_multiseg"] and feats["far_overlap"] and feats["off_1"] and feats["off_3"], feats
+    check_str(dec, v, codecs=[nat.ZSTD])
 
 
 def test_string_dict_expands_payload(dec):

@@ -70,13 +70,18 @@ def test_fuse_writer_shape_large(dec):
         assert n == 5
 
 
-@pytest.mark.parametrize("comp", ["SNAPPY", "LZ4"])
+@pytest.mark.parametrize("comp", ["SNAPPY", "LZ4", "ZSTD"])
 def test_far_back_references(dec, comp):
     """Matches farther back than the inflate kernel's 32 KiB LDS ring (read back from the page's
     own output in HBM), including an LZ4 match longer than its offset: a random 40 000-byte block
     repeated, then a 60 000-byte one with a few values changed.  pyarrow's LZ4 writes the first
     page as one literal and one 119 995-byte match at offset 40 000; its Snappy skips ahead in
-    random bytes and finds none (that leg checks the literal path on the same data)."""
+    random bytes and finds none (that leg checks the literal path on the same data).  Its ZSTD
+    (libzstd 1.5.7, as the frame walker of tests/zstd_frames.py reads the pages) writes the first
+    page as two blocks: 40 000 raw literals and one 91 072-byte match at offset 40 000 — beyond
+    the Zstd decoder's 16 KiB ring, read from the output, longer than its offset — then the
+    remaining 28 928 bytes as a second match at the same (repeated) offset; the second page holds
+    nine more matches at offsets up to 84 000 among 2 555 short ones at offset 1."""
     import pyarrow as pa
     rng = np.random.default_rng(11)
     a = rng.integers(-2**62, 2**62, 5_000)

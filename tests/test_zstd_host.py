@@ -2,8 +2,10 @@
 checked against libzstd-made frames (pyarrow's zstd codec: levels 1-19 and negative, raw / RLE /
 compressed blocks, Huffman 1- and 4-stream literals, predefined / RLE / FSE / repeat sequence
 tables), plus corrupted frames under AddressSanitizer: every malformed input is rejected without
-an out-of-bounds access.  The GPU parity of the same decoder on Parquet pages is
-tests/test_gpu_parquet.py."""
+an out-of-bounds access.  The case table of tests/zstd_frames.py (frames built to reach every
+decoder path, and malformed ones) runs through a stand-alone AddressSanitizer + UBSan program,
+tests/csrc/zstd_host_main.cpp.  The GPU parity of the same decoder on Parquet pages is
+tests/test_gpu_parquet.py and tests/test_gpu_zstd_frames.py."""
 import ctypes as C
 import os
 import subprocess
@@ -99,3 +101,42 @@ print("silent", bad_ok)
     r = subprocess.run(["python", "-c", script], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "ERROR: AddressSanitizer" not in r.stderr
+
+
+# ---- the host build under AddressSanitizer + UBSan, as a program of its own ------------------------
+def _fnv1a64(b: bytes) -> int:
+    h = 0xcbf29ce484222325
+    for x in np.frombuffer(b, np.uint8).tolist():
+        h = ((h ^ x) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def test_case_table_under_sanitizers_standalone(tmp_path):
+    """tests/csrc/zstd_host_main.cpp (its own main; nothing sanitised is loaded into this process):
+    every frame of the case table (tests/zstd_frames.py) and every malformed frame, each in a heap
+    block of exactly its length and decoded into one of exactly the output size, in one run.  The
+    good frames decode to the expected bytes (by hash), the malformed ones are rejected, and
+    neither sanitizer reports anything."""
+    import struct
+
+    from tests import zstd_frames as zf
+    exe = str(tmp_path / "zstd_host_main")
+    build = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            "-fno-omit-frame-pointer", "-I", CSRC, os.path.join(HERE, "csrc", "zstd_host_main.cpp"), "-o", exe],
+                           capture_output=True, text=True)
+    if build.returncode != 0 and "cannot find" in build.stderr and ("asan" in build.stderr or "ubsan" in build.stderr):
+        pytest.skip("no host AddressSanitizer / UBSan runtime to link against")
+    assert build.returncode == 0, build.stderr[-3000:]
+    good, bad = zf.cases(), zf.malformed()
+    recs = [(c.frame, len(c.expected)) for c in good] + [(m.frame, m.size) for m in bad]
+    (tmp_path / "records.bin").write_bytes(struct.pack("<I", len(recs)) +
+                                           b"".join(struct.pack("<IQ", len(f), n) + f for f, n in recs))
+    run = subprocess.run([exe, str(tmp_path / "records.bin"), str(tmp_path / "out.txt")], capture_output=True, text=True, timeout=300,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert run.returncode == 0, run.stderr[-3000:]
+    assert "ERROR" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-3000:]
+    got = (tmp_path / "out.txt").read_text().split("\n")[:-1]
+    assert len(got) == len(recs)
+    exp = ["0 %016x" % _fnv1a64(c.expected) for c in good] + ["1"] * len(bad)
+    wrong = [(n, g, e) for n, g, e in zip([c.name for c in good] + [m.name for m in bad], got, exp) if g != e]
+    assert not wrong, wrong[:5]
