@@ -7,4 +7,12 @@ ctypes, plus the multi-GPU exchange over torch.distributed (RCCL).
 """
 from .column import Column, DataBlock, DataType  # noqa: F401
 
-__all__ = ["Column", "DataBlock", "DataType"]
+__all__ = ["Column", "DataBlock", "DataType", "PartialSingleStateAggregator", "FinalSingleStateAggregator"]
+
+
+def __getattr__(name):
+    # the processors without GROUP BY, resolved on first use (the aggregator module binds the library)
+    if name in ("PartialSingleStateAggregator", "FinalSingleStateAggregator"):
+        from . import aggregator
+        return getattr(aggregator, name)
+    raise AttributeError(name)

@@ -28,6 +28,20 @@ STRATEGY_AUTO, STRATEGY_TABLE, STRATEGY_PARTITIONED = range(3)
 INSERT_PATHS = ("generic", "generic_lenpred", "fast", "fast_pred", "str1", "str1_pred", "short",
                 "pp_generic", "pp_fixed", "pp_str")
 
+# Aggregation without GROUP BY (a handle with no group columns, csrc/reduce.hpp): rows one
+# workgroup takes per trip and the grid cap of a reduce launch (KEYLESS_TILE, KEYLESS_MAX_BLOCKS)
+KEYLESS_TILE = 8192
+KEYLESS_MAX_BLOCKS = 2048
+
+
+def declare_keyless(L):
+    """argtypes of the keyless handle's own entry point (ffi.lib() calls this).  A library loaded
+    through DBGPU_LIB may predate it (scripts/bench_keyless.py's baseline side): calling it there
+    fails with ctypes' AttributeError, nothing stands in for it."""
+    if hasattr(L, "dbg_agg_keyless_stats"):
+        L.dbg_agg_keyless_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+
+
 # dbg_cmp
 CMP_EQ, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE = range(6)
 

@@ -9,6 +9,8 @@ Names, argument meaning and error behaviour follow the reference
 * `TransformPartialAggregate`   AGG/transform_aggregate_partial.rs:107-468 (transform / on_finish)
 * `TransformFinalAggregate`     AGG/transform_aggregate_final.rs:45-343 (transform -> DataBlock)
 * `AggregateMeta`               AGG/aggregate_meta.rs:124-134 (partial payloads between stages)
+* `PartialSingleStateAggregator` / `FinalSingleStateAggregator`
+                                AGG/transform_single_key.rs (no GROUP BY: one state per aggregate)
 
 Every call lands in libdbgpu_agg.so; the product path has no CPU fallback.
 """
@@ -174,7 +176,9 @@ def _arg_structs(aggs: Sequence[AggregateFunction], params: Sequence[Optional[Co
 
 
 class AggregateHashTable:
-    """One GPU aggregate table (a `dbg_agg_handle`)."""
+    """One GPU aggregate table (a `dbg_agg_handle`).  With `group_data_types == []` it is the keyless
+    handle of include/dbgpu_agg.h: one state, add_groups([], args, ...), a one-row merge_result()
+    and result_serialized(), merge_serialized(states, [], rows)."""
 
     def __init__(self, params: AggregatorParams, config: HashTableConfig = None, device: int = -1, stream=None):
         config = config or HashTableConfig()
@@ -271,13 +275,24 @@ class AggregateHashTable:
         check(lib().dbg_agg_insert_paths(self.h, counts, n))
         return dict(zip(abi.INSERT_PATHS, (int(c) for c in counts)))
 
+    def keyless_stats(self) -> dict:
+        """A table without group columns: reduce launches and serialized states merged since it was
+        created (dbg_agg_keyless_stats; host bookkeeping)."""
+        r, m = C.c_uint64(), C.c_uint64()
+        check(lib().dbg_agg_keyless_stats(self.h, C.byref(r), C.byref(m)))
+        return {"reduce_launches": r.value, "merged_states": m.value}
+
     # ---- AggregateHashTable::add_groups (+ fused filter)
     def add_groups(self, group_columns: Sequence[ColumnLike], params: Sequence[Optional[ColumnLike]],
                    rows: Optional[int] = None, filter_program=None, on_device: Optional[bool] = None) -> None:
+        # no group columns (a keyless table): the rows and the residence of the first argument column
+        lead = list(group_columns) + [p for p in params if p is not None]
         if rows is None:
-            rows = len(group_columns[0])
+            if not lead:
+                raise ValueError("add_groups without any column needs rows")
+            rows = len(lead[0])
         if on_device is None:
-            on_device = not isinstance(group_columns[0], Column)
+            on_device = bool(lead) and not isinstance(lead[0], Column)
         keys = abi_array([c.to_abi() for c in group_columns])
         args = _arg_structs(self.params.aggregate_functions, params)
         fp = filter_program.ptr() if filter_program is not None else None
@@ -322,8 +337,15 @@ class AggregateHashTable:
         for i, b in enumerate(keys):
             out_k[i].data, out_k[i].offsets, out_k[i].validity = b["ptrs"]
         check(lib().dbg_agg_result(self.h, out_a, out_k, 0))
+        self._release_keyless_inputs()
         cols = [self._to_column(b, n) for b in aggs] + [self._to_column(b, n) for b in keys]
         return DataBlock(cols)
+
+    def _release_keyless_inputs(self):
+        """A keyless table references no input row after the batch's own kernels: once a result call
+        has synchronised the stream, the device inputs retained so far may go."""
+        if not self.params.group_data_types:
+            self._retained.clear()
 
     def merge_result_device(self) -> list:
         """All groups as device columns [agg results..., group cols...] (DeviceColumn, HBM): only the
@@ -370,6 +392,7 @@ class AggregateHashTable:
         for i, b in enumerate(keys):
             out_k[i].data, out_k[i].offsets, out_k[i].validity = b["ptrs"]
         check(lib().dbg_agg_result_serialized(self.h, out_a, out_k, 0))
+        self._release_keyless_inputs()
         cols = [self._to_column(b, n) for b in states] + [self._to_column(b, n) for b in keys]
         return DataBlock(cols)
 
@@ -409,10 +432,11 @@ class AggregateHashTable:
         """add_groups with agg_states: AggregateMeta::Serialized's block re-inserted with batch_merge
         (SerializedPayload::convert_to_aggregate_table, AGG/aggregate_meta.rs:57-101).
         state_columns: one Binary column of borsh states per aggregate."""
+        lead = list(group_columns) + list(state_columns or [])
         if rows is None:
-            rows = len(group_columns[0])
+            rows = len(lead[0])
         if on_device is None:
-            on_device = not isinstance(group_columns[0], Column)
+            on_device = not isinstance(lead[0], Column)
         keys = abi_array([c.to_abi() for c in group_columns])
         states = abi_array([c.to_abi() for c in state_columns]) if state_columns else None
         check(lib().dbg_agg_merge_serialized(self.h, states, keys, rows, 1 if on_device else 0))
@@ -615,6 +639,7 @@ class TransformPartialAggregate:
 
     def __init__(self, params: AggregatorParams, config: HashTableConfig = None, device: int = -1,
                  staging_rows: int = DEFAULT_STAGING_ROWS, compact_bytes: int = DEFAULT_COMPACT_BYTES):
+        _refuse_keyless(params, "TransformPartialAggregate", "PartialSingleStateAggregator")
         self.params = params
         self.config = (config or HashTableConfig()).with_partial(True)
         self.distinct = None
@@ -766,6 +791,7 @@ class TransformFinalAggregate:
     [agg results..., group cols...]."""
 
     def __init__(self, params: AggregatorParams, device: int = -1):
+        _refuse_keyless(params, "TransformFinalAggregate", "FinalSingleStateAggregator")
         self.params = params
         self.device = device
 
@@ -792,6 +818,81 @@ class TransformFinalAggregate:
                 else:
                     p = m.payload
                     final.merge_records(p.records, p.strings, [p.n_records], [p.string_bytes])
+            return final.merge_result()
+        finally:
+            final.close()
+
+
+def _refuse_keyless(params: AggregatorParams, what: str, instead: str) -> None:
+    """The grouped processors bucket by group hash; without group columns the pipeline builder picks
+    the single-state processors (builder_aggregate.rs: params.group_columns.is_empty())."""
+    if not params.group_data_types and not any(f.distinct for f in params.aggregate_functions):
+        from .ffi import Unsupported
+        raise Unsupported(abi.DBG_ERR_UNSUPPORTED, f"{what}: no group columns; use {instead}")
+
+
+class PartialSingleStateAggregator:
+    """AGG/transform_single_key.rs:43-133 — `SELECT COUNT | SUM FROM table`: one state per aggregate,
+    here the keyless handle's.  transform accumulates a block (func.accumulate(place, columns, None,
+    rows), :104-106), on_finish emits one row of Binary states (:113-131).  Host blocks are gathered
+    by the library's host staging, as TransformPartialAggregate does."""
+
+    DEFAULT_STAGING_ROWS = TransformPartialAggregate.DEFAULT_STAGING_ROWS
+
+    def __init__(self, params: AggregatorParams, device: int = -1, staging_rows: int = DEFAULT_STAGING_ROWS):
+        if params.group_data_types:
+            raise ValueError("PartialSingleStateAggregator: the params have group columns")
+        self.params = params
+        self.state = AggregateHashTable(params, HashTableConfig(True), device)
+        if staging_rows:
+            self.state.set_host_staging(staging_rows)
+
+    @classmethod
+    def try_new(cls, params: AggregatorParams, device: int = -1, **kw):
+        return cls(params, device, **kw)
+
+    def transform(self, block: DataBlock, arg_indices: Sequence[Optional[int]], filter_program=None) -> List[DataBlock]:
+        args = [None if i is None else block.columns[i] for i in arg_indices]
+        self.state.add_groups([], args, rows=block.num_rows(), filter_program=filter_program)
+        return []
+
+    def on_finish(self) -> List[DataBlock]:
+        """One one-row DataBlock of Binary state columns, also when no row was accumulated."""
+        return [self.state.result_serialized()]
+
+    def close(self):
+        self.state.close()
+
+
+class FinalSingleStateAggregator:
+    """AGG/transform_single_key.rs:136-250 — collects the partials' one-row state blocks
+    (transform, :188-197) and on_finish merges every one of them into fresh states
+    (batch_merge_single, :223-227) and emits the one result row, also when it collected nothing
+    (:212-245)."""
+
+    def __init__(self, params: AggregatorParams, device: int = -1):
+        if params.group_data_types:
+            raise ValueError("FinalSingleStateAggregator: the params have group columns")
+        self.params = params
+        self.device = device
+        self.to_merge: List[DataBlock] = []
+
+    @classmethod
+    def try_create(cls, params: AggregatorParams, device: int = -1):
+        return cls(params, device)
+
+    def transform(self, block: DataBlock) -> List[DataBlock]:
+        if block.num_rows():
+            self.to_merge.append(block)
+        return []
+
+    def on_finish(self) -> DataBlock:
+        final = AggregateHashTable(self.params, HashTableConfig(False), self.device)
+        try:
+            blocks, self.to_merge = self.to_merge, []
+            na = len(self.params.aggregate_functions)
+            for b in blocks:
+                final.merge_serialized(b.columns[:na], [], rows=b.num_rows())
             return final.merge_result()
         finally:
             final.close()

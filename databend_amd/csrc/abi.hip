@@ -434,6 +434,25 @@ int part_flush(dbg_agg_handle* h) {
     return DBG_OK;
 }
 
+// A keyless handle's batch (func.accumulate(place, columns, None, rows), AGG/transform_single_key.rs:
+// 104-106): the reduce into per-workgroup partial states, then their merge into the state.  Nothing
+// reads the batch's rows after these two kernels.
+static int keyless_add(dbg_agg_handle* h, u32 bid, u64 rows, int on_device) {
+    const u32 blocks = keyless_grid(rows);
+    {
+        prof::Scope ps("keyless_reduce", h->stream);
+        launch_keyless_reduce(h->stream, h->dspec, h->dbatches + bid, rows, h->kpartials, blocks);
+    }
+    {
+        prof::Scope ps("keyless_merge", h->stream);
+        launch_keyless_merge(h->stream, h->dspec, h->kpartials, blocks, (u32)h->spec.stride_words, h->kstate);
+    }
+    HIPCHECK(hipGetLastError());
+    h->kl_reduces++;
+    if (!on_device) HIPCHECK(hipStreamSynchronize(h->stream));  // host path: synchronous like the reference processor
+    return DBG_OK;
+}
+
 static int add_groups_now(dbg_agg_handle* h, const dbg_column* group_cols, const dbg_column* arg_cols, const dbg_filter* filter,
                           uint64_t rows, int on_device) {
     if (rows >= 0xFFFFFFFFULL) return fail(DBG_ERR_UNSUPPORTED, "a batch holds fewer than 2^32 rows");
@@ -461,6 +480,7 @@ static int add_groups_now(dbg_agg_handle* h, const dbg_column* group_cols, const
     }
     if (filter && filter->n_nodes) RETURN_IF(fill_filter(own, filter, on_device, rows, st->fcols, &st->n_fcols, st->nodes, &st->n_nodes));
     RETURN_IF(submit_batch(h, &st, &bid, on_device && h->owned.size() == owned0));
+    if (is_keyless(S)) return keyless_add(h, bid, rows, on_device);
     // high cardinality: the radix-partitioned payload instead of the HBM table (pp.hip)
     if (!h->pp) RETURN_IF(pp_maybe_switch(h, bid, rows));
     if (h->pp) return pp_add_batch(h, st, bid, rows, 0);
@@ -580,6 +600,18 @@ int dbg_agg_create(const dbg_agg_params* params, dbg_agg_handle** out) {
     if (hipMemcpy(h->dspec, &h->spec, sizeof(Spec), hipMemcpyHostToDevice) != hipSuccess) return cleanup(fail(DBG_ERR_DEVICE, "spec upload"));
     if ((rc = h->hcounters.ensure(CNT_WORDS + DBG_MAX_KEYS + 8)) != DBG_OK) return cleanup(rc);
     if (hipHostGetDevicePointer((void**)&h->hcounters_dev, h->hcounters.get(), 0) != hipSuccess) h->hcounters_dev = nullptr;
+    if (is_keyless(h->spec)) {  // one state and a launch's partial states instead of the table
+        if ((rc = h->kstate.ensure((u64)h->spec.stride_words)) != DBG_OK) return cleanup(rc);
+        if ((rc = h->kpartials.ensure((u64)KEYLESS_MAX_BLOCKS * (u64)h->spec.stride_words)) != DBG_OK) return cleanup(rc);
+        launch_keyless_init(h->stream, h->dspec, h->kstate);
+        BatchDesc* st0;
+        u32 bid0;
+        if ((rc = new_batch(h, &st0, &bid0)) != DBG_OK) return cleanup(rc);
+        h->n_batches = 0;
+        if (hipStreamSynchronize(h->stream) != hipSuccess) return cleanup(fail(DBG_ERR_DEVICE, "sync"));
+        *out = h;
+        return DBG_OK;
+    }
     // initial capacity: 2x the hint, or 1024 slots (the CPU table starts at 32768 =
     // AggregateHashTable::initial_capacity(); on the GPU growth is a cheap rehash kernel and a
     // small table keeps init / finalize scans short for low-cardinality queries: 4096 -> 1024
@@ -648,6 +680,11 @@ int dbg_agg_reset(dbg_agg_handle* h) {
     h->n_batches = h->n_cached;  // cached descriptors stay valid (immutable)
     h->pending_rows = h->pending_recs = 0;
     h->finalized = false;
+    if (is_keyless(h->spec)) {  // the state back to its initial words, in stream order
+        prof::Scope ps("keyless_init", h->stream);
+        launch_keyless_init(h->stream, h->dspec, h->kstate);
+        return DBG_OK;
+    }
     h->table_rows = 0;
     h->remerged = 0;
     h->xrecv_busy = false;  // no group references the exchange's receive buffers any more
@@ -671,7 +708,7 @@ int dbg_agg_reset(dbg_agg_handle* h) {
 
 int dbg_agg_add_groups(dbg_agg_handle* h, const dbg_column* group_cols, const dbg_column* arg_cols, const dbg_filter* filter,
                        uint64_t rows, int on_device) {
-    if (!h || !group_cols) return fail(DBG_ERR_INVALID, "null argument");
+    if (!h || (!group_cols && h->spec.n_keys)) return fail(DBG_ERR_INVALID, "null argument");
     HIPCHECK(hipSetDevice(h->device));
     hstage::Stage& G = h->stage;
     if (on_device || !G.cap || rows >= G.cap) {
@@ -716,6 +753,7 @@ int dbg_agg_set_host_staging(dbg_agg_handle* h, uint64_t rows) {
 int dbg_agg_set_strategy(dbg_agg_handle* h, int strategy) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
     if (strategy < DBG_STRATEGY_AUTO || strategy > DBG_STRATEGY_PARTITIONED) return fail(DBG_ERR_INVALID, "unknown strategy");
+    if (strategy == DBG_STRATEGY_PARTITIONED) REFUSE_KEYLESS(h, "dbg_agg_set_strategy(PARTITIONED)");
     if (strategy == DBG_STRATEGY_PARTITIONED) REFUSE_HANDLE_LOCAL(h, "dbg_agg_set_strategy(PARTITIONED)");
     if (h->table_rows || h->ppk[0].l1_n || h->ppk[1].l1_n)
         return fail(DBG_ERR_INVALID, "dbg_agg_set_strategy: the handle holds groups (call it after create or reset)");
@@ -755,6 +793,7 @@ int dbg_agg_insert_paths(dbg_agg_handle* h, uint64_t* counts, int32_t n) {
 
 int dbg_agg_set_partition_keys(dbg_agg_handle* h, int n_keys) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
+    REFUSE_KEYLESS(h, "dbg_agg_set_partition_keys");
     if (n_keys < 0 || n_keys > h->spec.n_keys) return fail(DBG_ERR_INVALID, "partition keys: 0..n_group_cols");
     h->part_keys = n_keys;
     return DBG_OK;
@@ -762,13 +801,23 @@ int dbg_agg_set_partition_keys(dbg_agg_handle* h, int n_keys) {
 
 int dbg_agg_set_recycle(dbg_agg_handle* h, int on) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
+    if (on) REFUSE_KEYLESS(h, "dbg_agg_set_recycle(1)");
     h->recycle = on ? 1 : 0;
     return DBG_OK;
 }
 
 int dbg_agg_capacity(dbg_agg_handle* h, uint64_t* slots) {
     if (!h || !slots) return fail(DBG_ERR_INVALID, "null argument");
+    REFUSE_KEYLESS(h, "dbg_agg_capacity");
     *slots = h->cap;
+    return DBG_OK;
+}
+
+int dbg_agg_keyless_stats(dbg_agg_handle* h, uint64_t* reduce_launches, uint64_t* merged_states) {
+    if (!h) return fail(DBG_ERR_INVALID, "null handle");
+    if (!is_keyless(h->spec)) return fail(DBG_ERR_INVALID, "dbg_agg_keyless_stats: the handle has group columns");
+    if (reduce_launches) *reduce_launches = h->kl_reduces;
+    if (merged_states) *merged_states = h->kl_merged;
     return DBG_OK;
 }
 }  // extern "C"

@@ -152,12 +152,16 @@ static int result_impl(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_colu
         if (is_str_minmax(S.aggs[a])) rc = tmp(n * 8, &od.agg_data[a]);  // row references, gathered below
         else rc = dest(out_aggs[a].data, n * type_width(t.type), &od.agg_data[a]);
         if (rc == DBG_OK && t.nullable) {
-            if (agg_always_valid(S.aggs[a])) od.all_valid |= 1u << a;
+            // (a keyless result is NULL for the empty input, whatever the argument)
+            if (agg_always_valid(S.aggs[a]) && !is_keyless(S)) od.all_valid |= 1u << a;
             else rc = tmp(n, (void**)&od.agg_valid[a]);
         }
     }
     RETURN_IF(rc);
-    if (h->pp) {
+    if (is_keyless(S)) {
+        prof::Scope ps("keyless_write", h->stream);
+        launch_keyless_write(h->stream, h->dspec, h->kstate, od, h->counters + CNT_ERR);
+    } else if (h->pp) {
         prof::Scope ps("pp_write", h->stream);
         launch_pp_grec_write(h->stream, h->dspec, h->dbatches, h->pp_grec, h->pp_tot, h->pp_blk, h->pp_nb, od,
                              h->counters + CNT_ERR);
@@ -460,6 +464,16 @@ int dbg_agg_finalize(dbg_agg_handle* h, uint64_t* n_groups, uint64_t* string_byt
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(flush_pending(h));
+    if (is_keyless(h->spec)) {
+        // one row always, from freshly initialised states when no row ever reached them
+        // (FinalSingleStateAggregator::on_finish, AGG/transform_single_key.rs:212-245)
+        h->n_groups = 1;
+        h->string_bytes.clear();
+        h->agg_string_bytes.assign(h->spec.n_aggs, 0);
+        h->finalized = true;
+        if (n_groups) *n_groups = 1;
+        return DBG_OK;
+    }
     if (h->pp) return pp_finalize(h, n_groups, string_bytes);
     const Spec& S = h->spec;
     // Optimistic single round trip: count + scan are enqueued behind the inserts and read back
@@ -527,7 +541,9 @@ int dbg_agg_finalize_into(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_c
 
 int dbg_agg_finalize_into_async(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg_out_column* out_keys, uint64_t max_groups,
                                 const uint64_t* max_string_bytes) {
-    if (!h || !out_aggs || !out_keys) return fail(DBG_ERR_INVALID, "null argument");
+    if (!h || !out_aggs) return fail(DBG_ERR_INVALID, "null argument");
+    REFUSE_KEYLESS(h, "dbg_agg_finalize_into_async");
+    if (!out_keys) return fail(DBG_ERR_INVALID, "null argument");
     // String MIN/MAX: no room for the aggregates' string sizes.  Decimal256 results go through the
     // same writers as dbg_agg_result, so that handle-local spec is served here.
     if (has_str_minmax(h->spec))
@@ -544,7 +560,9 @@ int dbg_agg_finalize_into_async(dbg_agg_handle* h, dbg_out_column* out_aggs, dbg
 int dbg_agg_step_async(dbg_agg_handle* h, const dbg_column* group_cols, const dbg_column* arg_cols, const dbg_filter* filter,
                        uint64_t rows, dbg_out_column* out_aggs, dbg_out_column* out_keys, uint64_t max_groups,
                        const uint64_t* max_string_bytes) {
-    if (!h || !group_cols || !out_aggs || !out_keys) return fail(DBG_ERR_INVALID, "null argument");
+    if (!h) return fail(DBG_ERR_INVALID, "null argument");
+    REFUSE_KEYLESS(h, "dbg_agg_step_async");
+    if (!group_cols || !out_aggs || !out_keys) return fail(DBG_ERR_INVALID, "null argument");
     if (has_str_minmax(h->spec))
         return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_agg_step_async: ") + handle_local_reason(h->spec));
     if (h->fin.active) return fail(DBG_ERR_INVALID, "a finalize is already in flight: dbg_agg_finalize_wait first");

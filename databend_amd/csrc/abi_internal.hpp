@@ -4,7 +4,9 @@
 // The units: abi.hip the handle itself (error slot, table, batches, inserts), abi_spec.hip specs and
 // layouts, abi_pp.hip the partitioned payload's host side, abi_finalize.hip both finalize families,
 // abi_records.hip records / partition / merge / compact, abi_ops.hip the handle-free entry points,
-// prof.hip the event profiler, exchange.hip the multi-GPU exchange over RCCL.
+// prof.hip the event profiler, exchange.hip the multi-GPU exchange over RCCL.  A handle without group
+// columns (is_keyless) is one state instead of a table: its kernels are reduce.hip's, its host steps
+// sit in the same units beside the table's (keyless_add, keyless_merge_serialized, result_impl).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,6 +24,7 @@
 #include "host_stage.hpp"
 #include "legacy.hpp"
 #include "serde.hpp"
+#include "reduce.hpp"
 
 #include "filter.hpp"
 #include "like.hpp"
@@ -241,6 +244,12 @@ struct dbg_agg_handle {
 
     // host-block staging (dbg_agg_set_host_staging, host_stage.hpp)
     hstage::Stage stage;
+
+    // ---- keyless handle (no group columns, reduce.hpp): one state instead of the table ----
+    Buf<u64> kstate;     // spec.stride_words words, slot layout (word 0 unused)
+    Buf<u64> kpartials;  // KEYLESS_MAX_BLOCKS rows of stride_words: a reduce launch's per-workgroup states
+    u64 kl_reduces = 0;  // reduce launches / serialized states merged since create (dbg_agg_keyless_stats)
+    u64 kl_merged = 0;
 };
 
 // Handle-local specs.  Records, the partitioned payload, the exchanges and the serialized states
@@ -271,6 +280,15 @@ inline const char* handle_local_reason(const Spec& S) {
     do {                                                                                      \
         if (const char* why_ = handle_local_reason((h)->spec))                                \
             return fail(DBG_ERR_UNSUPPORTED, std::string(what) + ": " + why_);               \
+    } while (0)
+
+// A keyless handle (no group columns) has one state and no hash, table, records or partitions:
+// every entry point that needs one of them refuses it (REFUSE_KEYLESS).
+inline bool is_keyless(const Spec& S) { return S.n_keys == 0; }
+inline const char* keyless_reason() { return "the handle has no group columns (one state: no hash table, records or partitions)"; }
+#define REFUSE_KEYLESS(h, what)                                                                                     \
+    do {                                                                                                            \
+        if (is_keyless((h)->spec)) return fail(DBG_ERR_UNSUPPORTED, std::string(what) + ": " + keyless_reason()); \
     } while (0)
 
 inline void note_insert(dbg_agg_handle* h, InsertPath p) {

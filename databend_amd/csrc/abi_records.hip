@@ -74,9 +74,38 @@ static int merge_record_batch(dbg_agg_handle* h, const u8* base, u64 n, const u8
     return DBG_OK;
 }
 
+// `rows` serialized states per aggregate -> the keyless handle's state (batch_merge_single,
+// AGG/transform_single_key.rs:223-227): decoded into word rows, checked, then folded by the merge
+// kernel.  The word rows are a temporary; nothing is retained.
+static int keyless_merge_serialized(dbg_agg_handle* h, const SerIngest& in, u64 rows) {
+    const Spec& S = h->spec;
+    Buf<u64> words;
+    RETURN_IF(words.ensure(rows * (u64)S.stride_words));
+    if (!h->ser_err) RETURN_IF(h->ser_err.ensure(1));
+    HIPCHECK(hipMemsetAsync(h->ser_err, 0, 8, h->stream));
+    {
+        prof::Scope ps("keyless_decode", h->stream);
+        launch_keyless_decode(h->stream, h->dspec, in, rows, words, h->ser_err);
+    }
+    HIPCHECK(hipGetLastError());
+    u64 e = 0;
+    HIPCHECK(hipMemcpyAsync(&e, h->ser_err, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    if (e & ERR_SER_MALFORMED) return fail(DBG_ERR_INVALID, "serialized state bytes do not match the aggregate's state layout");
+    {
+        prof::Scope ps("keyless_merge", h->stream);
+        launch_keyless_merge(h->stream, h->dspec, words, rows, (u32)S.stride_words, h->kstate);
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(h->stream));  // the word rows are freed behind it
+    h->kl_merged += rows;
+    return DBG_OK;
+}
+
 extern "C" {
 int dbg_agg_partition(dbg_agg_handle* h, uint32_t n_parts, int scheme, uint64_t* rec_counts, uint64_t* string_bytes) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
+    REFUSE_KEYLESS(h, "dbg_agg_partition");
     REFUSE_HANDLE_LOCAL(h, "dbg_agg_partition");
     if (n_parts < 1 || n_parts > 256) return fail(DBG_ERR_UNSUPPORTED, "1..256 partitions");
     if (scheme < 0 || scheme > 2) return fail(DBG_ERR_INVALID, "scheme 0 (hash % n), 1 (radix bits) or 2 (legacy buckets)");
@@ -149,6 +178,7 @@ int dbg_agg_partition(dbg_agg_handle* h, uint32_t n_parts, int scheme, uint64_t*
 
 int dbg_agg_export_records(dbg_agg_handle* h, void* dev_records, void* dev_strings) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
+    REFUSE_KEYLESS(h, "dbg_agg_export_records");
     REFUSE_HANDLE_LOCAL(h, "dbg_agg_export_records");
     if (!h->part_n) return fail(DBG_ERR_INVALID, "dbg_agg_partition must precede dbg_agg_export_records");
     HIPCHECK(hipSetDevice(h->device));
@@ -167,7 +197,9 @@ int dbg_agg_export_records(dbg_agg_handle* h, void* dev_records, void* dev_strin
 
 // ---- fixed-capacity exchange (replicas + gather, low cardinality) ----
 int dbg_agg_export_fixed(dbg_agg_handle* h, void* dev_buf, uint64_t cap_records) {
-    if (!h || !dev_buf) return fail(DBG_ERR_INVALID, "null argument");
+    if (!h) return fail(DBG_ERR_INVALID, "null argument");
+    REFUSE_KEYLESS(h, "dbg_agg_export_fixed");
+    if (!dev_buf) return fail(DBG_ERR_INVALID, "null argument");
     REFUSE_HANDLE_LOCAL(h, "dbg_agg_export_fixed");
     const Spec& S = h->spec;
     if (!S.inline_keys) return fail(DBG_ERR_UNSUPPORTED, "fixed export needs fixed-width (inline) group keys");
@@ -183,7 +215,9 @@ int dbg_agg_export_fixed(dbg_agg_handle* h, void* dev_buf, uint64_t cap_records)
 }
 
 int dbg_agg_merge_fixed(dbg_agg_handle* h, const void* dev_bufs, int32_t n_bufs, uint64_t cap_records) {
-    if (!h || !dev_bufs || n_bufs < 1) return fail(DBG_ERR_INVALID, "bad argument");
+    if (!h) return fail(DBG_ERR_INVALID, "bad argument");
+    REFUSE_KEYLESS(h, "dbg_agg_merge_fixed");
+    if (!dev_bufs || n_bufs < 1) return fail(DBG_ERR_INVALID, "bad argument");
     REFUSE_HANDLE_LOCAL(h, "dbg_agg_merge_fixed");
     const Spec& S = h->spec;
     if (!S.inline_keys) return fail(DBG_ERR_UNSUPPORTED, "fixed merge needs fixed-width (inline) group keys");
@@ -212,6 +246,7 @@ int dbg_agg_merge_fixed(dbg_agg_handle* h, const void* dev_bufs, int32_t n_bufs,
 int dbg_agg_merge_records(dbg_agg_handle* h, const void* dev_records, const void* dev_strings, int32_t n_segments,
                           const uint64_t* seg_records, const uint64_t* seg_string_bytes) {
     if (!h) return fail(DBG_ERR_INVALID, "null handle");
+    REFUSE_KEYLESS(h, "dbg_agg_merge_records");
     REFUSE_HANDLE_LOCAL(h, "dbg_agg_merge_records");
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(flush_pending(h));
@@ -289,7 +324,7 @@ int dbg_agg_retained_bytes(dbg_agg_handle* h, uint64_t* bytes) {
 // AGG/aggregate_meta.rs:57-101; AggregateFunction::batch_merge, EAGG/aggregate_function.rs:96-103).
 int dbg_agg_merge_serialized(dbg_agg_handle* h, const dbg_column* state_cols, const dbg_column* group_cols, uint64_t rows,
                              int on_device) {
-    if (!h || (!state_cols && h->spec.n_aggs) || !group_cols) return fail(DBG_ERR_INVALID, "null argument");
+    if (!h || (!state_cols && h->spec.n_aggs) || (!group_cols && h->spec.n_keys)) return fail(DBG_ERR_INVALID, "null argument");
     REFUSE_HANDLE_LOCAL(h, "dbg_agg_merge_serialized");
     HIPCHECK(hipSetDevice(h->device));
     RETURN_IF(flush_pending(h));
@@ -317,6 +352,7 @@ int dbg_agg_merge_serialized(dbg_agg_handle* h, const dbg_column* state_cols, co
         in.st_data[a] = d.data;
         in.st_offs[a] = d.offsets;
     }
+    if (is_keyless(S)) return keyless_merge_serialized(h, in, rows);
     // records are retained (the table's ref-key entries point at them) until reset
     RETURN_IF(own_alloc({h->stream, h->owned}, rows * S.rec_width));
     u8* const rb = h->owned.back();

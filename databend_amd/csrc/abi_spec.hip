@@ -64,8 +64,22 @@ static int result_type_of(const dbg_agg_spec& s, dbg_datatype* out) {
 int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtypes) {
     memset(&S, 0, sizeof(S));
     S.x_pp_cap = ~0u;  // no test hook (dbg_agg_create reads them)
-    if (p->n_group_cols < 1 || p->n_group_cols > DBG_MAX_KEYS) return fail(DBG_ERR_UNSUPPORTED, "1..8 group columns supported");
+    if (p->n_group_cols < 0 || p->n_group_cols > DBG_MAX_KEYS) return fail(DBG_ERR_UNSUPPORTED, "0..8 group columns supported");
     if (p->n_aggs < 0 || p->n_aggs > DBG_MAX_AGGS) return fail(DBG_ERR_UNSUPPORTED, "at most 32 aggregates");
+    // no group columns: one state (reduce.hpp).  The register kernel carries states of at most two
+    // words and no row references, and the empty input of an unwrapped function is not defined.
+    const bool keyless = p->n_group_cols == 0;
+    if (keyless) {
+        if (p->n_aggs == 0) return fail(DBG_ERR_UNSUPPORTED, "no group columns: at least one aggregate is needed");
+        for (int a = 0; a < p->n_aggs; ++a) {
+            const dbg_agg_spec& s = p->aggs[a];
+            if (s.kind != DBG_AGG_COUNT && !s.or_null)
+                return fail(DBG_ERR_UNSUPPORTED, "no group columns: every aggregate but COUNT needs or_null (the factory always wraps)");
+            if ((s.kind == DBG_AGG_MIN || s.kind == DBG_AGG_MAX) && s.arg.type == DBG_STRING)
+                return fail(DBG_ERR_UNSUPPORTED, "no group columns: MIN/MAX of a String argument is not supported");
+            if (s.arg.type == DBG_DECIMAL256) return fail(DBG_ERR_UNSUPPORTED, "no group columns: Decimal256 arguments are not supported");
+        }
+    }
     S.n_keys = p->n_group_cols;
     S.n_aggs = p->n_aggs;
     // inline packing: row format [validity bytes][values] (EAGG/payload.rs:100-129)
@@ -124,13 +138,18 @@ int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtyp
         }
         word += A.nwords;
         A.flag_bit = -1;
-        if ((s.kind == DBG_AGG_SUM || s.kind == DBG_AGG_MIN || s.kind == DBG_AGG_MAX) && A.arg_nullable) A.flag_bit = flag_bits++;
+        // (keyless: every one of them, since the empty input is NULL whatever the argument)
+        if ((s.kind == DBG_AGG_SUM || s.kind == DBG_AGG_MIN || s.kind == DBG_AGG_MAX) && (A.arg_nullable || keyless)) A.flag_bit = flag_bits++;
         A.res_type = rt.type;
         A.res_precision = rt.precision;
         A.res_scale = rt.scale;
         A.res_nullable = rt.nullable;
         // SUM's range check (DecimalSumState<OVERFLOW>, p <= 18) also guards AVG_SQL's sum
         A.dec_check = ((s.kind == DBG_AGG_SUM || sql_avg) && t == DBG_DECIMAL128 && s.arg.precision <= 18) ? 1 : 0;
+        // keyless: AVG's own range check at precision > 18 (DecimalAvgState<OVERFLOW = true>,
+        // aggregate_avg.rs:141-153), made by keyless_write_kernel on the final sum; the grouped
+        // writers read dec_check for SUM and AVG_SQL only
+        if (keyless && s.kind == DBG_AGG_AVG && t == DBG_DECIMAL128 && s.arg.precision > 18) A.dec_check = 1;
         A.scale_add = (A.kind == DBG_AGG_AVG && (t == DBG_DECIMAL128 || t == DBG_DECIMAL256)) ? (int)rt.scale - (int)s.arg.scale : 0;
         A.avg_round = sql_avg && t == DBG_DECIMAL128;
         A.res_width = (int)type_width(rt.type);
@@ -142,7 +161,7 @@ int build_spec(const dbg_agg_params* p, Spec& S, std::vector<dbg_datatype>& rtyp
         }
     }
     if (flag_bits > 64) return fail(DBG_ERR_UNSUPPORTED, "too many nullable aggregates");
-    S.flags_word = flag_bits ? word++ : -1;
+    S.flags_word = (flag_bits || keyless) ? word++ : -1;  // keyless: always, for KEYLESS_SEEN_BIT
     S.n_words = word - 1;
     if (word > DBG_MAX_WORDS) return fail(DBG_ERR_UNSUPPORTED, "aggregate states too wide");
     int sw = 1;
@@ -223,6 +242,7 @@ int dbg_agg_result_type(const dbg_agg_spec* spec, dbg_datatype* out) {
 
 int dbg_agg_record_width(dbg_agg_handle* h, uint32_t* width) {
     if (!h || !width) return fail(DBG_ERR_INVALID, "null argument");
+    REFUSE_KEYLESS(h, "dbg_agg_record_width");
     *width = h->spec.rec_width;
     return DBG_OK;
 }
@@ -232,6 +252,7 @@ int dbg_agg_record_layout(const dbg_agg_params* params, dbg_record_layout* out) 
     Spec S;
     std::vector<dbg_datatype> rt;
     RETURN_IF(build_spec(params, S, rt));
+    if (is_keyless(S)) return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_agg_record_layout: ") + keyless_reason());
     if (const char* why = handle_local_reason(S)) return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_agg_record_layout: ") + why);
     memset(out, 0, sizeof(*out));
     out->width = S.rec_width;

@@ -162,6 +162,7 @@ static void payload_owned(u32 d, u32 n, u32& lo, u32& hi) {
 }
 
 static int payload_check(dbg_agg_handle* h) {
+    REFUSE_KEYLESS(h, "payload exchange");
     REFUSE_HANDLE_LOCAL(h, "payload exchange");
     if (!h->pp) return fail(DBG_ERR_UNSUPPORTED, "payload exchange: the handle is not in partitioned mode (dbg_agg_set_strategy)");
     if (h->spec.pp_str) return fail(DBG_ERR_UNSUPPORTED, "payload exchange: string keys (records may reference local rows)");
@@ -367,6 +368,7 @@ int dbg_payload_exchange_plan(const dbg_agg_params* params, uint32_t n_ranks, ui
     Spec S;
     std::vector<dbg_datatype> rt;
     RETURN_IF(build_spec(params, S, rt));
+    if (is_keyless(S)) return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_payload_exchange_plan: ") + keyless_reason());
     if (const char* why = handle_local_reason(S)) return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_payload_exchange_plan: ") + why);
     const uint32_t w[2] = {S.pp_rw_raw, S.pp_rw_state};
     if (widths) {
@@ -401,6 +403,7 @@ static int all_ok(dbg_comm* c, RcclApi& R, hipStream_t s, bool ok, int* bad_rank
 }
 
 int dbg_agg_exchange_payload(dbg_comm* c, dbg_agg_handle* h, dbg_exchange_stats* stats) {
+    if (h) REFUSE_KEYLESS(h, "payload exchange");  // (before the communicator is looked at)
     if (!c || !h) return fail(DBG_ERR_INVALID, "null argument");
     REFUSE_HANDLE_LOCAL(h, "payload exchange");
     if (h->device != c->device) return fail(DBG_ERR_INVALID, "communicator and table are on different devices");
@@ -490,6 +493,7 @@ int dbg_agg_exchange_payload(dbg_comm* c, dbg_agg_handle* h, dbg_exchange_stats*
 // overlap the transfer.  The last call (last = 1) waits for every transfer and makes what arrived
 // the payload (one level-1 segment per chunk and source), like dbg_agg_exchange_payload.
 int dbg_agg_exchange_payload_chunk(dbg_comm* c, dbg_agg_handle* h, int last, dbg_exchange_stats* stats) {
+    if (h) REFUSE_KEYLESS(h, "payload exchange");  // (before the communicator is looked at)
     if (!c || !h) return fail(DBG_ERR_INVALID, "null argument");
     REFUSE_HANDLE_LOCAL(h, "payload exchange");
     if (h->device != c->device) return fail(DBG_ERR_INVALID, "communicator and table are on different devices");
@@ -629,6 +633,7 @@ int dbg_merge_exchange_plan(const dbg_agg_params* params, uint32_t n_ranks, uint
     Spec S;
     std::vector<dbg_datatype> rt;
     RETURN_IF(build_spec(params, S, rt));
+    if (is_keyless(S)) return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_merge_exchange_plan: ") + keyless_reason());
     if (const char* why = handle_local_reason(S)) return fail(DBG_ERR_UNSUPPORTED, std::string("dbg_merge_exchange_plan: ") + why);
     if (record_width) *record_width = S.rec_width;
     merge_plan(n_ranks, rank, S.rec_width, all_sizes, send_bytes, recv_bytes, recv_records);
@@ -648,6 +653,8 @@ static int xrecv_buffer(dbg_agg_handle* fh, int k, u64 bytes, void** out) {
 }
 
 int dbg_agg_exchange(dbg_comm* c, dbg_agg_handle* partial, dbg_agg_handle* final_h, dbg_exchange_stats* stats) {
+    if (partial) REFUSE_KEYLESS(partial, "dbg_agg_exchange");  // (before the communicator is looked at)
+    if (final_h) REFUSE_KEYLESS(final_h, "dbg_agg_exchange");
     if (!c || !partial || !final_h) return fail(DBG_ERR_INVALID, "null argument");
     REFUSE_HANDLE_LOCAL(partial, "dbg_agg_exchange");
     REFUSE_HANDLE_LOCAL(final_h, "dbg_agg_exchange");

@@ -432,6 +432,45 @@ enum {
 };
 int dbg_agg_insert_paths(dbg_agg_handle* h, uint64_t* counts, int32_t n);
 
+/* ---- aggregation without GROUP BY: the keyless handle (PartialSingleStateAggregator /
+ *      FinalSingleStateAggregator, AGG/transform_single_key.rs) ----
+ * dbg_agg_create with n_group_cols == 0 (group_types may be NULL) and 1..32 aggregates gives a handle
+ * with ONE state and no table.  COUNT, SUM, MIN, MAX, AVG and AVG_SQL over every argument type of
+ * the grouped path, except: n_aggs == 0, an aggregate other than COUNT with or_null == 0 (the
+ * factory always wraps, FUN/aggregate_function_factory.rs:157-164), MIN/MAX of a String and any
+ * Decimal256 argument — DBG_ERR_UNSUPPORTED, the message naming "no group columns".
+ *   dbg_agg_add_groups(h, NULL, arg_cols, filter, rows, on_device): func.accumulate(place, columns,
+ *     None, rows) (:104-106) of the rows that pass the fused filter (LIKE nodes included); host
+ *     blocks and dbg_agg_set_host_staging work; rows == 0 is a no-op.  Nothing references the
+ *     input rows after the batch's own kernels: on-device inputs need to outlive only the stream
+ *     work of their own call, not the handle.
+ *   dbg_agg_finalize: *n_groups = 1 always, also when no row was added or none passed the filter
+ *     (on_finish emits one row from freshly initialised states, :212-245).
+ *   dbg_agg_result: one row per aggregate, out_keys ignored (may be NULL).  The empty input gives
+ *     COUNT = 0 and NULL everywhere else.  Decimal range checks / DBG_ERR_OVERFLOW as on the
+ *     grouped path, on the final sum.
+ *   dbg_agg_serialized_stride / dbg_agg_result_serialized: one row of borsh states (what the
+ *     partial's on_finish emits, :113-131).  The NullUnary adaptor's byte is 1 iff a non-NULL value
+ *     was accumulated; the OrNull adaptor's byte is 1 iff at least one row passed the filter,
+ *     whatever the argument's validity (adaptors/aggregate_ornull_adaptor.rs:108-126).
+ *   dbg_agg_merge_serialized(h, state_cols, NULL, rows, on_device): batch_merge_single (:223-227) of
+ *     `rows` states per aggregate.  A state with OrNull byte 0 or None merges as "nothing seen" (the
+ *     reference's keyless partial writes it for the empty input); malformed lengths are
+ *     DBG_ERR_INVALID.
+ *   dbg_agg_reset, dbg_agg_set_stream, dbg_agg_destroy work; dbg_agg_compact is a no-op
+ *     (*compacted = 0); dbg_agg_retained_bytes counts the copies of host blocks only.
+ * Everything that needs a hash or a table returns DBG_ERR_UNSUPPORTED naming "no group columns":
+ * dbg_agg_set_strategy(DBG_STRATEGY_PARTITIONED), dbg_agg_partition / dbg_agg_export_records /
+ * dbg_agg_merge_records, dbg_agg_export_fixed / dbg_agg_merge_fixed, every dbg_agg_payload_* and
+ * dbg_agg_exchange* entry point and both exchange plans, dbg_agg_record_layout /
+ * dbg_agg_record_width, dbg_agg_set_partition_keys, dbg_agg_set_recycle(1), dbg_agg_capacity,
+ * dbg_agg_finalize_into(_async) and dbg_agg_step_async.
+ *
+ * dbg_agg_keyless_stats: reduce launches (one per non-empty batch that reached the device) and
+ * serialized states merged, cumulative since dbg_agg_create.  Host bookkeeping only: the call
+ * never touches the device.  DBG_ERR_INVALID on a handle with group columns. */
+int dbg_agg_keyless_stats(dbg_agg_handle* h, uint64_t* reduce_launches, uint64_t* merged_states);
+
 /* ---- partial-state records: exchange / partition bucket (EAGG/payload.rs:356-391,
  *      EAGG/partitioned_payload.rs:100-143, AGG/aggregate_exchange_injector.rs:154-235) ----
  * A record = [hash u64][group keys, fixed part][state words]; string keys are (u64 offset, u64 len)
