@@ -7,7 +7,8 @@ ctypes, plus the multi-GPU exchange over torch.distributed (RCCL).
 """
 from .column import Column, DataBlock, DataType  # noqa: F401
 
-__all__ = ["Column", "DataBlock", "DataType", "PartialSingleStateAggregator", "FinalSingleStateAggregator"]
+__all__ = ["Column", "DataBlock", "DataType", "PartialSingleStateAggregator", "FinalSingleStateAggregator",
+           "ExprProgram", "col", "lit"]
 
 
 def __getattr__(name):
@@ -15,4 +16,8 @@ def __getattr__(name):
     if name in ("PartialSingleStateAggregator", "FinalSingleStateAggregator"):
         from . import aggregator
         return getattr(aggregator, name)
+    # the projection in front of the aggregate (expr.py)
+    if name in ("ExprProgram", "col", "lit"):
+        from . import expr
+        return getattr(expr, name)
     raise AttributeError(name)

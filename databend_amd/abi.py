@@ -86,6 +86,31 @@ class dbg_filter(C.Structure):
                 ("n_cols", C.c_int32), ("cols", C.POINTER(dbg_column))]
 
 
+# dbg_expr_op, and the caps of a dbg_expr_program (live stack values: DBG_EXPR_STACK in csrc/expr.hpp)
+EXPR_COLUMN, EXPR_CONST, EXPR_PLUS, EXPR_MINUS, EXPR_MULTIPLY, EXPR_STORE = range(6)
+EXPR_MAX_NODES, EXPR_MAX_COLUMNS, EXPR_MAX_OUTPUTS, EXPR_MAX_STACK = 64, 16, 8, 4
+
+
+class dbg_expr_node(C.Structure):
+    _fields_ = [("op", C.c_int32), ("index", C.c_int32), ("dt", dbg_datatype), ("i64", C.c_int64),
+                ("f64", C.c_double), ("i128_lo", C.c_uint64), ("i128_hi", C.c_int64)]
+
+
+class dbg_expr_program(C.Structure):
+    _fields_ = [("nodes", C.POINTER(dbg_expr_node)), ("n_nodes", C.c_int32), ("n_cols", C.c_int32),
+                ("cols", C.POINTER(dbg_column)), ("n_outputs", C.c_int32), ("reserved", C.c_int32)]
+
+
+def declare_expr(L):
+    """argtypes of the projection's entry points (ffi.lib() calls this).  A library loaded through
+    DBGPU_LIB may predate them (scripts/bench_expr.py's baseline side): calling them there fails
+    with ctypes' AttributeError, nothing stands in for them."""
+    if hasattr(L, "dbg_expr_eval"):
+        L.dbg_expr_result_type.argtypes = [C.POINTER(dbg_expr_program), C.c_int32, C.POINTER(dbg_datatype)]
+        L.dbg_expr_eval.argtypes = [C.POINTER(dbg_expr_program), C.POINTER(dbg_filter), C.c_uint64,
+                                    C.POINTER(dbg_out_column), C.c_void_p]
+
+
 class dbg_agg_params(C.Structure):
     _fields_ = [("group_types", C.POINTER(dbg_datatype)), ("n_group_cols", C.c_int32),
                 ("aggs", C.POINTER(dbg_agg_spec)), ("n_aggs", C.c_int32), ("device", C.c_int32),
@@ -122,5 +147,5 @@ DBG_COMM_ID_BYTES = 128
 EXPECTED_SIZES = {
     "dbg_datatype": 8, "dbg_column": 56, "dbg_out_column": 32, "dbg_agg_spec": 16,
     "dbg_pred_node": 64, "dbg_filter": 24, "dbg_agg_params": 48, "dbg_record_layout": 328, "dbg_exchange_stats": 32,
-    "dbg_parquet_chunk": 40, "dbg_native_column": 48,
+    "dbg_parquet_chunk": 40, "dbg_native_column": 48, "dbg_expr_node": 48, "dbg_expr_program": 32,
 }

@@ -4,7 +4,8 @@
 // The units: abi.hip the handle itself (error slot, table, batches, inserts), abi_spec.hip specs and
 // layouts, abi_pp.hip the partitioned payload's host side, abi_finalize.hip both finalize families,
 // abi_records.hip records / partition / merge / compact, abi_ops.hip the handle-free entry points,
-// prof.hip the event profiler, exchange.hip the multi-GPU exchange over RCCL.  A handle without group
+// prof.hip the event profiler, exchange.hip the multi-GPU exchange over RCCL, expr.hip the projection
+// (its kernel and its two entry points together).  A handle without group
 // columns (is_keyless) is one state instead of a table: its kernels are reduce.hip's, its host steps
 // sit in the same units beside the table's (keyless_add, keyless_merge_serialized, result_impl).
 #pragma once

@@ -29,6 +29,7 @@ EXPORTED = [
     "dbg_agg_payload_import_chunks", "dbg_agg_exchange_payload_chunk",
     "dbg_scan_create", "dbg_scan_destroy", "dbg_parquet_chunk_rows", "dbg_parquet_decode",
     "dbg_agg_keyless_stats", "dbg_native_decode", "dbg_like_pattern_kind", "dbg_like_match_host", "dbg_like_kernel_counts", "dbg_like_force_kernel",
+    "dbg_expr_result_type", "dbg_expr_eval",
 ]
 
 
@@ -142,6 +143,7 @@ def lib():
         L.dbg_like_force_kernel.argtypes = [I32]
         L.dbg_datagen.argtypes = [C.c_int, U64, U64, U64, P(VP), C.c_int, VP, VP]
         abi.declare_keyless(L)
+        abi.declare_expr(L)
         _LIB = L
     return _LIB
 

@@ -646,6 +646,92 @@ int dbg_agg_merge_fixed(dbg_agg_handle* h, const void* dev_bufs, int32_t n_bufs,
  * *n_sel its count (synchronous). */
 int dbg_filter_select(const dbg_filter* filter, uint64_t rows, uint32_t* sel_out, uint64_t* n_sel,
                       void* hip_stream);
+/* ---- scalar projection: plus / minus / multiply in front of the aggregate ----
+ * The seam: the projection the planner puts before an aggregate whose arguments or group keys are
+ * expressions — BlockOperator::Map (src/query/sql/src/evaluator/block_operator.rs:50-80) calls
+ * Evaluator::run and appends the result columns that TransformPartialAggregate then indexes.  Here
+ * the result columns are written to caller-allocated device buffers and go into
+ * dbg_agg_add_groups(..., on_device = 1) as arguments or keys as they are.
+ *
+ * A program is postfix over its own columns, like dbg_filter:
+ *   DBG_EXPR_COLUMN   push column `index`
+ *   DBG_EXPR_CONST    push the constant of type `dt` (not nullable): integers in i64 (unsigned: the
+ *                     u64 bits), floats in f64, Decimal128 in (i128_hi:i128_lo) at dt's scale
+ *   DBG_EXPR_PLUS / _MINUS / _MULTIPLY   pop b, pop a, push a op b
+ *   DBG_EXPR_STORE    write the top of the stack to output `index` without popping it, so a later
+ *                     operator can take the stored value (TPC-H Q1's charge reuses disc_price)
+ * At the end every output 0..n_outputs-1 has been stored exactly once and every value still on the
+ * stack has been stored.  A stored value that no later operator takes does not count as live after
+ * its last STORE.  Caps: DBG_EXPR_MAX_NODES nodes, DBG_EXPR_MAX_COLUMNS columns,
+ * DBG_EXPR_MAX_OUTPUTS outputs, 4 live values — beyond them DBG_ERR_UNSUPPORTED.  Stack underflow,
+ * a value left over (neither stored nor used), an output stored twice or never, a bad column or
+ * output index, an unknown op: DBG_ERR_INVALID.
+ *
+ * Types and values follow the reference exactly (FUNCS = src/query/functions/src/scalars):
+ *  - numbers (FUNCS/arithmetic.rs:91-175): plus / multiply give an integer of min(64, 2 x the wider
+ *    operand) bits, signed if either operand is; minus the same width, always signed; a Float32 or
+ *    Float64 operand makes the result Float64.  Operands convert as Rust's `as`; 64-bit integer
+ *    results wrap (the reference's release build; nothing else in it pins the case); every float
+ *    operation rounds on its own.
+ *  - Decimal128 (EXP/types/decimal.rs:1000-1067, FUNCS/decimal/arithmetic.rs:75-172): an integer
+ *    operand is the decimal of get_decimal_properties (EXP/types/number.rs:475-484).  plus / minus:
+ *    (min(38, max(la, lb) + s + 1), s = max(sa, sb)); operands are cast to that type, a cast that
+ *    raises the scale is range-checked (FUNCS/decimal/cast.rs:686-707), the result is range-checked
+ *    only at precision 38.  multiply: s = min(sa + sb, max(sa, sb, 12)), p = min(38, la + lb + s),
+ *    value do_round_mul (decimal.rs:465-478), an error only outside the i128 range.
+ *  - NULLs (EXP/function.rs:562-571, 660-710): a result is nullable if any operand is, its validity
+ *    the AND of theirs; a NULL row raises nothing and its data bytes are unspecified.
+ * Refused with DBG_ERR_UNSUPPORTED and a message naming it: Decimal256, String, Boolean, Date and
+ * Timestamp operands, Decimal mixed with Float, NULL constants.  Division, modulo, unary minus,
+ * casts and functions have no op. */
+typedef enum {
+    DBG_EXPR_COLUMN = 0,
+    DBG_EXPR_CONST = 1,
+    DBG_EXPR_PLUS = 2,
+    DBG_EXPR_MINUS = 3,
+    DBG_EXPR_MULTIPLY = 4,
+    DBG_EXPR_STORE = 5
+} dbg_expr_op;
+
+#define DBG_EXPR_MAX_NODES 64
+#define DBG_EXPR_MAX_COLUMNS 16
+#define DBG_EXPR_MAX_OUTPUTS 8
+
+typedef struct dbg_expr_node {
+    int32_t op;      /* dbg_expr_op */
+    int32_t index;   /* COLUMN: index into dbg_expr_program.cols; STORE: output */
+    dbg_datatype dt; /* CONST */
+    int64_t i64;
+    double f64;
+    uint64_t i128_lo;
+    int64_t i128_hi;
+} dbg_expr_node;
+
+typedef struct dbg_expr_program {
+    const dbg_expr_node* nodes; /* postfix */
+    int32_t n_nodes;
+    int32_t n_cols;
+    const dbg_column* cols;
+    int32_t n_outputs;
+    int32_t reserved;
+} dbg_expr_program;
+
+/* The type of output k: the one place expression types are decided (as dbg_agg_result_type is for
+ * aggregates).  Host only, no device needed: the program is checked and typed from its columns'
+ * dt alone, their data pointers are not read. */
+int dbg_expr_result_type(const dbg_expr_program* program, int32_t k, dbg_datatype* out);
+/* Evaluator::run of the program over `rows` rows of device-resident columns (views may start at
+ * any element and any validity bit offset).  outs[k] (n_outputs entries): dt is filled by the
+ * library; data holds rows x width bytes, validity ceil(rows / 8) bytes written from bit 0, only
+ * for nullable results.  filter (may be NULL): the TransformFilter in front of the projection —
+ * only rows where the predicate is TRUE can raise, the other rows' outputs are unspecified (a
+ * dbg_agg_add_groups with the same filter never reads them); LIKE nodes as in dbg_filter_select.
+ * Synchronous on hip_stream: an error on any valid, selected row (ErrorCode::Overflow, "Decimal
+ * overflow" / "Decimal multiply overflow") fails the call with DBG_ERR_OVERFLOW, the message
+ * naming the operation; the outputs are then unspecified. */
+int dbg_expr_eval(const dbg_expr_program* program, const dbg_filter* filter, uint64_t rows, dbg_out_column* outs,
+                  void* hip_stream);
+
 /* ---- LIKE on the host (no device needed): the classification and the matcher the kernels run ----
  * dbg_like_pattern_kind: *kind = the dbg_like_kind generate_like_pattern (EXP/filter/like.rs:186-248)
  * gives the raw pattern.  dbg_like_match_host: *out = 1 when str LIKE pat by the reference's
