@@ -357,7 +357,7 @@ def decode_chunk(chunk: bytes, ptype: int, codec: int, max_def: int, tlen: int =
         defs = rle_hybrid(buf, dp, de, 1, n) if max_def else np.ones(n, dtype=np.uint32)
         nn = int(defs.sum())
         if pg.encoding in (PLAIN_DICTIONARY, RLE_DICTIONARY):
-            bw = buf[vp]
+            bw = buf[vp] if vp < len(buf) else 0  # a page of NULLs may carry no index bytes, not even the width
             idx = rle_hybrid(buf, vp + 1, len(buf), bw, nn) if bw else np.zeros(nn, dtype=np.uint32)
             vals = [dictionary[i] for i in idx]
         elif pg.encoding == PLAIN:
