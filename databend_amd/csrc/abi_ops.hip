@@ -201,6 +201,7 @@ int dbg_sort_limit_indices(const dbg_column* col, uint64_t rows, int asc, int nu
     REFUSE_DECIMAL256(t, "dbg_sort_limit_indices");
     if (t == DBG_STRING || t == DBG_DECIMAL128 || type_width(t) == 0)
         return fail(DBG_ERR_UNSUPPORTED, "dbg_sort_limit_indices: fixed-width number columns only");
+    if (col->len < rows) return fail(DBG_ERR_INVALID, "column shorter than rows");
     std::string err;
     int rc = sort_limit_run((hipStream_t)stream, dcol_view(*col), rows, asc, nulls_first, limit, idx_out, n_out, err);
     return rc == DBG_OK ? rc : fail(rc, err);

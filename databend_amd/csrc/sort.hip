@@ -311,7 +311,8 @@ int sort_limit_run(hipStream_t s, const DCol& c, u64 rows, int asc, int nulls_fi
 // NULLs), then the value — 8 bytes of the order key for numbers, 16 for Decimal128, and for a
 // String its bytes in groups of 8, each followed by a marker byte (9 = more groups follow, else the
 // group's byte count), which makes the encoding prefix-free and byte-wise comparison equal to
-// (bytes, length) order; DESC inverts the value bytes.  A NULL's value bytes are 0.  The radix
+// (bytes, length) order; DESC inverts the value bytes.  A NULL's value bytes are 0, and a NULL
+// String is exactly one zero group, so a NULL takes the same room in every row.  The radix
 // select of the single-column path then runs over (key words..., row index): per word an AND/OR
 // pass finds the bytes every row in play shares, one histogram pass per remaining byte picks the
 // bucket of the limit-th row, and words already decided are matched whole.  The <= limit rows
@@ -322,7 +323,9 @@ __device__ __forceinline__ u32 mkey_col_len(const MKeyDesc& K, int c, u64 row) {
     const DCol& col = K.cols[c];
     u32 n = col.nullable ? 1u : 0u;
     if (col.type == DBG_STRING) {
-        const u64 len = dcol_str(col, row).len;
+        // a NULL is one zero group whatever bytes lie under it: the next column starts at the
+        // same byte in every NULL row (mkey_col_byte writes zeros for as many bytes as this says)
+        const u64 len = dcol_valid(col, row) ? dcol_str(col, row).len : 0;
         return n + 9u * (u32)(len ? (len + 7) / 8 : 1);
     }
     return n + (col.type == DBG_DECIMAL128 ? 16u : 8u);

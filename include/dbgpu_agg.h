@@ -784,7 +784,8 @@ int dbg_legacy_group_hash(const dbg_column* cols, int n, uint64_t rows, uint64_t
  * values by ord::total_cmp (integers) / total_cmp_f32|f64 (floats, IEEE totalOrder), reversed when
  * asc == 0; equal values in ascending row order (the reference leaves their order unspecified:
  * select_nth_unstable_by).  *n_out = min(limit, rows).  limit > 2048, Decimal128 and STRING
- * columns return DBG_ERR_UNSUPPORTED.  Synchronous on hip_stream. */
+ * columns return DBG_ERR_UNSUPPORTED; col->len < rows returns DBG_ERR_INVALID (as a short column
+ * does in dbg_sort_limit_multi).  Synchronous on hip_stream. */
 int dbg_sort_limit_indices(const dbg_column* col, uint64_t rows, int asc, int nulls_first, uint64_t limit,
                            uint32_t* idx_out, uint64_t* n_out, void* hip_stream);
 /* ORDER BY several columns LIMIT k: DataBlock::sort with n_cols descriptions (EXP/kernels/sort.rs:
