@@ -87,8 +87,17 @@ class dbg_filter(C.Structure):
 
 
 # dbg_expr_op, and the caps of a dbg_expr_program (live stack values: DBG_EXPR_STACK in csrc/expr.hpp)
-EXPR_COLUMN, EXPR_CONST, EXPR_PLUS, EXPR_MINUS, EXPR_MULTIPLY, EXPR_STORE = range(6)
+EXPR_COLUMN, EXPR_CONST, EXPR_PLUS, EXPR_MINUS, EXPR_MULTIPLY, EXPR_STORE, EXPR_FUNC = range(7)
 EXPR_MAX_NODES, EXPR_MAX_COLUMNS, EXPR_MAX_OUTPUTS, EXPR_MAX_STACK = 64, 16, 8, 4
+
+# dbg_expr_func, in the header's order from 1 (0 is not a function): the reference's function names
+EXPR_FUNC_NAMES = ("to_yyyymm", "to_yyyymmdd", "to_yyyymmddhh", "to_yyyymmddhhmmss", "to_year", "to_quarter", "to_month",
+                   "to_day_of_month", "to_day_of_week", "to_day_of_year", "to_week_of_year", "to_unix_timestamp", "to_hour",
+                   "to_minute", "to_second", "to_start_of_second", "to_start_of_minute", "to_start_of_five_minutes",
+                   "to_start_of_ten_minutes", "to_start_of_fifteen_minutes", "time_slot", "to_start_of_hour", "to_start_of_day",
+                   "to_monday", "to_start_of_week", "to_start_of_month", "to_start_of_quarter", "to_start_of_year",
+                   "to_start_of_iso_year", "length")
+EXPR_FUNCS = {name: i + 1 for i, name in enumerate(EXPR_FUNC_NAMES)}
 
 
 class dbg_expr_node(C.Structure):

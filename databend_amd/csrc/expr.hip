@@ -1,5 +1,6 @@
 // expr.hip — the device projection (dbg_expr_result_type / dbg_expr_eval): plus, minus and multiply
-// over numbers and Decimal128 in front of the aggregate (BlockOperator::Map, expr.hpp has the rules).
+// over numbers and Decimal128, the date / time functions and length() in front of the aggregate
+// (BlockOperator::Map, expr.hpp has the rules).
 //
 // A streaming element-wise kernel, memory-bound by intent.  The host lowers the program to ENodes
 // (expr_compile); the kernel walks them per strip with wave-uniform dispatch and keeps the operand
@@ -13,6 +14,11 @@
 //           bytes per lane, the validity bytes of a wave's 64 rows come from a ballot.
 // The last partial strip is read row by row behind a bound check.  An error (a decimal overflow on
 // a valid, selected row) is raised with one plain store per workgroup.
+// A third template flag, FUNC, compiles the date / time functions into the node loop (one more
+// wave-uniform case, element-wise on the canonical value); a program without one runs the
+// instantiation without them, whose code is what it was before the functions existed.
+// length() is a pre-pass of its own (expr_length_kernel below): it writes a UInt64 column into a
+// temporary of the call, which the node loop then reads as an ordinary column leaf.
 #include "abi_internal.hpp"
 #include "expr.hpp"
 
@@ -241,7 +247,7 @@ __device__ __forceinline__ void expr_copy(ESlot<WIDE, R>& d, const ESlot<WIDE, R
 
 // The program over the lane's rows [r0, r0 + n).  `sel`: bit j = row j passed the filter.  Returns
 // 0, or 1 + the arithmetic op (EX_*) of an operator that failed on a valid, selected row.
-template <bool WIDE, int R, bool FULL, int DEPTH>
+template <bool WIDE, int R, bool FULL, int DEPTH, bool FUNC>
 __device__ __forceinline__ u32 expr_run(const EProg* __restrict__ P, u64 r0, int n, u32 sel) {
     ESlot<WIDE, R> s0, s1, s2, s3;  // s0 is the top of the stack
 #pragma unroll
@@ -281,6 +287,11 @@ __device__ __forceinline__ u32 expr_run(const EProg* __restrict__ P, u64 r0, int
                     expr_copy(s2, s3);
                 }
             }
+        } else if (FUNC && op == EX_FUNC) {
+            // one value in, one out: validity and the slots below stay as they are
+#pragma unroll
+            for (int j = 0; j < R; ++j) s0.lo[j] = expr_func(nd, s0.lo[j]);
+            if constexpr (WIDE) s0.hi[0] = expr_num_hi(nd, s0.lo[0]);
         } else {
             const u32 valid = s1.valid & s0.valid;
             if (op == EX_NUM) {
@@ -304,7 +315,7 @@ __device__ __forceinline__ u32 expr_run(const EProg* __restrict__ P, u64 r0, int
     return err;
 }
 
-template <bool WIDE, int DEPTH>
+template <bool WIDE, int DEPTH, bool FUNC>
 __global__ void __launch_bounds__(EXPR_BLOCK) expr_kernel(const EProg* __restrict__ P, const FilterDesc* __restrict__ F,
                                                            u32* __restrict__ err_out) {
     constexpr int R = WIDE ? 1 : 8;
@@ -326,13 +337,96 @@ __global__ void __launch_bounds__(EXPR_BLOCK) expr_kernel(const EProg* __restric
                 if (j < n && eval_pred(F->nodes, F->n_nodes, F->cols, r0 + j)) sel |= 1u << j;
         }
         u32 e;
-        if (WIDE || n < R) e = expr_run<WIDE, R, false, DEPTH>(P, r0, n, sel);  // wide: whole waves stay together for the ballot
-        else e = expr_run<WIDE, R, true, DEPTH>(P, r0, n, sel);
+        if (WIDE || n < R) e = expr_run<WIDE, R, false, DEPTH, FUNC>(P, r0, n, sel);  // wide: whole waves stay together for the ballot
+        else e = expr_run<WIDE, R, true, DEPTH, FUNC>(P, r0, n, sel);
         if (e) err = e;
     }
     if (err) s_err = err;  // any one of the workgroup's errors
     __syncthreads();
     if (threadIdx.x == 0 && s_err) *err_out = s_err;  // one plain store per workgroup
+}
+
+// ------------------------------------------------------------------------------------------
+// length(String): the number of bytes that are not UTF-8 continuation bytes, one UInt64 per row
+// ------------------------------------------------------------------------------------------
+// A workgroup takes LEN_ROWS consecutive rows, whose bytes are one contiguous span of the blob, and
+// streams the span in tiles of 256 aligned 16-byte chunks, one 16-byte load per lane.  Per chunk it
+// keeps a 16-bit mask of the bytes that start a character (inside the span) and the exclusive prefix
+// of their counts in LDS.  The count of start bytes from the span's first byte up to a row boundary
+// x is then  (start bytes of the tiles before) + prefix[chunk of x] + popcount(mask[chunk of x]
+// below x);  every boundary lies in exactly one tile, a lane resolves the boundaries it owns there,
+// and a row's length is the difference of its two boundaries.  No lane ever walks a string: a long
+// string only means more tiles for its workgroup, an empty one costs nothing.
+// LDS: 256 masks + 256 prefixes (u32) + (LEN_ROWS + 1) boundary counts (u64) + 4 wave totals:
+// 2 KiB + 8 KiB + 24 B.  Offsets are 64-bit and absolute, so a view may start at any row.
+#define LEN_ROWS 1024
+#define LEN_TILE (EXPR_BLOCK * 16)
+#define LEN_BOUNDS ((LEN_ROWS + EXPR_BLOCK) / EXPR_BLOCK)  // boundaries a lane owns: 5 (the last one only lane 0's)
+
+// bit k of the result: byte k of the four words starts a character
+__device__ __forceinline__ u32 len_start_mask(expr_u32x4 w) {
+    return expr_char_starts(w.x) | expr_char_starts(w.y) << 4 | expr_char_starts(w.z) << 8 | expr_char_starts(w.w) << 12;
+}
+
+__global__ void __launch_bounds__(EXPR_BLOCK) expr_length_kernel(const u8* __restrict__ data, const u64* __restrict__ offsets, u64 rows,
+                                                                  u64* __restrict__ out) {
+    __shared__ u32 s_mask[EXPR_BLOCK];
+    __shared__ u32 s_pre[EXPR_BLOCK];
+    __shared__ u32 s_wave[EXPR_BLOCK / 64];
+    __shared__ u64 s_bound[LEN_ROWS + 1];
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u64 r0 = (u64)blockIdx.x * LEN_ROWS;
+    if (r0 >= rows) return;
+    const u32 nr = (u32)(rows - r0 < (u64)LEN_ROWS ? rows - r0 : (u64)LEN_ROWS);  // rows of this workgroup: boundaries 0..nr
+    // the boundaries this lane owns, as absolute addresses
+    u64 x[LEN_BOUNDS];
+#pragma unroll
+    for (int k = 0; k < LEN_BOUNDS; ++k) {
+        const u32 i = tid + (u32)k * EXPR_BLOCK;
+        x[k] = i <= nr ? (u64)(uintptr_t)data + gld<u64>(offsets + r0 + i) : ~0ULL;
+        if (i <= nr) s_bound[i] = 0;
+    }
+    const u64 a0 = (u64)(uintptr_t)data + gld<u64>(offsets + r0), a1 = (u64)(uintptr_t)data + gld<u64>(offsets + r0 + nr);
+    u64 before = 0;  // start bytes of the tiles before this one
+    for (u64 t0 = a0 & ~15ULL; t0 <= a1; t0 += LEN_TILE) {
+        const u64 ca = t0 + 16ULL * tid;
+        // the chunk's bytes [lo, hi) lie in the span; a chunk with none is not loaded
+        const u32 lo = ca < a0 ? (u32)(a0 - ca) : 0u;
+        const u32 hi = ca >= a1 ? 0u : (a1 - ca < 16 ? (u32)(a1 - ca) : 16u);
+        u32 m = 0;
+        if (hi > lo) m = len_start_mask(gld<expr_u32x4>((const void*)(uintptr_t)ca)) & ((1u << hi) - 1u) & ~((1u << lo) - 1u);
+        const u32 cnt = (u32)__popc(m);
+        u32 inc = cnt;  // inclusive scan over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const u32 y = (u32)__shfl_up((int)inc, d, 64);
+            if (lane >= (u32)d) inc += y;
+        }
+        if (lane == 63) s_wave[wave] = inc;
+        __syncthreads();
+        u32 base = 0, total = 0;
+#pragma unroll
+        for (u32 w = 0; w < EXPR_BLOCK / 64; ++w) {
+            const u32 t = s_wave[w];
+            if (w < wave) base += t;
+            total += t;
+        }
+        s_mask[tid] = m;
+        s_pre[tid] = base + inc - cnt;
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < LEN_BOUNDS; ++k) {
+            if (x[k] >= t0 && x[k] - t0 < LEN_TILE) {
+                const u32 q = (u32)(x[k] - t0) >> 4, e = (u32)(x[k] - t0) & 15u;
+                s_bound[tid + (u32)k * EXPR_BLOCK] = before + s_pre[q] + (u32)__popc(s_mask[q] & ((1u << e) - 1u));
+            }
+        }
+        before += total;
+        // the next trip writes s_wave only after every lane is past the second barrier, and s_mask /
+        // s_pre only after its own first barrier, which every lane reaches after the loop above
+    }
+    __syncthreads();
+    for (u32 i = tid; i < nr; i += EXPR_BLOCK) gst<u64>(out + r0 + i, s_bound[i + 1] - s_bound[i]);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -345,11 +439,32 @@ struct ExprLaunch {
     Buf<FilterDesc> dfd;
     Buf<EProg> dp;
     Buf<u32> derr;
+    std::vector<Buf<u64>> lens;  // the columns length() pre-passes wrote
 };
 
 // Queue the filter's pre-passes, the uploads, the kernel and the read-back of the error word on s.
 // The caller synchronises s whatever this returns.
-static int expr_queue(const ExprCompiled& C, const EProg& E, const dbg_filter* filter, u64 rows, hipStream_t s, ExprLaunch& L, u32* err) {
+static int expr_queue(const ExprCompiled& C, EProg& E, const dbg_filter* filter, u64 rows, hipStream_t s, ExprLaunch& L, u32* err) {
+    // length(): every String column read through it becomes the UInt64 column of its lengths, the
+    // String column's validity passing through
+    for (int c = 0; c < E.n_cols; ++c) {
+        if (!(C.len_cols >> c & 1u)) continue;
+        L.lens.emplace_back();
+        RETURN_IF(L.lens.back().ensure(rows));
+        u64* out = L.lens.back().get();
+        {
+            prof::Scope ps("expr_length", s);
+            const u64 grid = (rows + LEN_ROWS - 1) / LEN_ROWS;
+            if (grid > 0x7fffffffULL) return fail(DBG_ERR_UNSUPPORTED, "expression program: too many rows for one length() pass");
+            hipLaunchKernelGGL(expr_length_kernel, dim3((u32)grid), dim3(EXPR_BLOCK), 0, s, E.cols[c].data, E.cols[c].offsets, rows, out);
+        }
+        HIPCHECK(hipGetLastError());
+        DCol& d = E.cols[c];
+        d.type = DBG_UINT64;
+        d.width = d.stride = 8;
+        d.data = (const u8*)out;
+        d.offsets = nullptr;
+    }
     const bool filtered = filter && filter->n_nodes;
     if (filtered) {
         L.hf.resize(1);
@@ -374,10 +489,19 @@ static int expr_queue(const ExprCompiled& C, const EProg& E, const dbg_filter* f
         const FilterDesc* f = filtered ? L.dfd.get() : nullptr;
         u32* derr = L.derr.get();
         const bool shallow = C.depth <= 2;  // two stack slots instead of four: fewer registers, more waves per SIMD
-        if (C.wide && shallow) hipLaunchKernelGGL((expr_kernel<true, 2>), dim3(grid), dim3(EXPR_BLOCK), 0, s, dp, f, derr);
-        else if (C.wide) hipLaunchKernelGGL((expr_kernel<true, 4>), dim3(grid), dim3(EXPR_BLOCK), 0, s, dp, f, derr);
-        else if (shallow) hipLaunchKernelGGL((expr_kernel<false, 2>), dim3(grid), dim3(EXPR_BLOCK), 0, s, dp, f, derr);
-        else hipLaunchKernelGGL((expr_kernel<false, 4>), dim3(grid), dim3(EXPR_BLOCK), 0, s, dp, f, derr);
+#define EXPR_LAUNCH(W, D, F) hipLaunchKernelGGL((expr_kernel<W, D, F>), dim3(grid), dim3(EXPR_BLOCK), 0, s, dp, f, derr)
+        if (C.has_func) {
+            if (C.wide && shallow) EXPR_LAUNCH(true, 2, true);
+            else if (C.wide) EXPR_LAUNCH(true, 4, true);
+            else if (shallow) EXPR_LAUNCH(false, 2, true);
+            else EXPR_LAUNCH(false, 4, true);
+        } else {
+            if (C.wide && shallow) EXPR_LAUNCH(true, 2, false);
+            else if (C.wide) EXPR_LAUNCH(true, 4, false);
+            else if (shallow) EXPR_LAUNCH(false, 2, false);
+            else EXPR_LAUNCH(false, 4, false);
+        }
+#undef EXPR_LAUNCH
     }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(err, L.derr, 4, hipMemcpyDeviceToHost, s));
@@ -411,7 +535,11 @@ int dbg_expr_eval(const dbg_expr_program* program, const dbg_filter* filter, uin
     for (int c = 0; c < program->n_cols; ++c) {
         const dbg_column& col = program->cols[c];
         if (col.len < rows) return fail(DBG_ERR_INVALID, "expression program: column shorter than rows");
-        if (rows && !col.data) return fail(DBG_ERR_INVALID, "expression program: column without data");
+        if (col.dt.type == DBG_STRING) {
+            if (rows && !col.offsets) return fail(DBG_ERR_INVALID, "expression program: String column without offsets");
+        } else if (rows && !col.data) {
+            return fail(DBG_ERR_INVALID, "expression program: column without data");
+        }
         E.cols[c] = dcol_view(col);
     }
     for (size_t k = 0; k < C.nodes.size(); ++k) E.nodes[k] = C.nodes[k];

@@ -1,9 +1,10 @@
 """Scalar expressions for the projection in front of the aggregate (mirror of the `Expr` trees that
 `BlockOperator::Map` evaluates, SQL/evaluator/block_operator.rs:50-80).
 
-`plus`, `minus` and `multiply` over number and Decimal128 columns and typed constants, evaluated on
-the device by dbg_expr_eval; the result columns stay in HBM and go into `add_groups` as arguments
-or group keys as they are.
+`plus`, `minus` and `multiply` over number and Decimal128 columns and typed constants, the date /
+time functions over Date and Timestamp columns (session timezone UTC) and `length` over String
+columns, evaluated on the device by dbg_expr_eval; the result columns stay in HBM and go into
+`add_groups` as arguments or group keys as they are.
 
     price, disc, tax = col(0), col(1), col(2)
     disc_price = price * (lit(1) - disc)
@@ -11,6 +12,11 @@ or group keys as they are.
     prog = ExprProgram([disc_price, charge], [extprice_col, discount_col, tax_col])
     prog.result_types()        # [Decimal(31, 4), Decimal(38, 6)]
     a, b = prog.eval(rows)     # DeviceColumns
+
+    minute = extract("minute", col(0))             # to_minute(EventTime): UInt8
+    bucket = date_trunc("minute", col(0))          # to_start_of_minute(EventTime): Timestamp
+    yyyymm = to_year(col(1)) * 100 + to_month(col(1))
+    url_len = length(col(2))                       # UInt64, NULL where the URL is
 """
 from __future__ import annotations
 
@@ -52,6 +58,11 @@ class Expr:
     def __rmul__(self, o):
         return _Bin("*", _wrap(o), self)
 
+    def func(self, name: str) -> "Expr":
+        """`name(self)` for a function of abi.EXPR_FUNC_NAMES; every one is also a method and a
+        module function of its own name: `e.to_year()`, `to_year(e)`."""
+        return _Func(name, self)
+
 
 class _Col(Expr):
     def __init__(self, index: int):
@@ -79,6 +90,63 @@ class _Bin(Expr):
 
     def children(self):
         return (self.a, self.b)
+
+
+class _Func(Expr):
+    def __init__(self, name: str, a: Expr):
+        if name not in abi.EXPR_FUNCS:
+            raise ValueError(f"no function {name!r}")
+        self.name, self.a = name, a
+        self._key = ("func", name, a.key())
+
+    def key(self):
+        return self._key
+
+    def children(self):
+        return (self.a,)
+
+
+def _define_functions():
+    for name in abi.EXPR_FUNC_NAMES:
+        def method(self, _name=name):
+            return _Func(_name, self)
+
+        def function(e, _name=name):
+            return _Func(_name, _wrap(e))
+        method.__name__ = function.__name__ = name
+        method.__doc__ = function.__doc__ = f"The reference's `{name}`."
+        setattr(Expr, name, method)
+        globals()[name] = function
+
+
+_define_functions()
+
+# date_trunc(unit, e): the to_start_of_* function the reference's rewrite picks; year, quarter and
+# month give a Date, the others a Timestamp
+_DATE_TRUNC = {"year": "to_start_of_year", "quarter": "to_start_of_quarter", "month": "to_start_of_month",
+               "day": "to_start_of_day", "hour": "to_start_of_hour", "minute": "to_start_of_minute",
+               "second": "to_start_of_second"}
+# extract(unit FROM e) / date_part: the to_* number function
+_EXTRACT = {"year": "to_year", "quarter": "to_quarter", "month": "to_month", "day": "to_day_of_month", "dow": "to_day_of_week",
+            "doy": "to_day_of_year", "week": "to_week_of_year", "hour": "to_hour", "minute": "to_minute", "second": "to_second",
+            "epoch": "to_unix_timestamp", "yyyymm": "to_yyyymm", "yyyymmdd": "to_yyyymmdd", "yyyymmddhh": "to_yyyymmddhh",
+            "yyyymmddhhmmss": "to_yyyymmddhhmmss"}
+
+
+def date_trunc(unit: str, e) -> Expr:
+    """`DATE_TRUNC(unit, e)`: sugar for the function the reference rewrites it to."""
+    u = unit.lower()
+    if u not in _DATE_TRUNC:
+        raise ValueError(f"date_trunc: no unit {unit!r}; one of {sorted(_DATE_TRUNC)}")
+    return _Func(_DATE_TRUNC[u], _wrap(e))
+
+
+def extract(unit: str, e) -> Expr:
+    """`EXTRACT(unit FROM e)`: sugar for the reference's `to_*` number function."""
+    u = unit.lower()
+    if u not in _EXTRACT:
+        raise ValueError(f"extract: no unit {unit!r}; one of {sorted(_EXTRACT)}")
+    return _Func(_EXTRACT[u], _wrap(e))
 
 
 def _wrap(v) -> Expr:
@@ -152,6 +220,9 @@ def postfix(exprs: Sequence[Expr]) -> List[dict]:
             out.append(dict(op=abi.EXPR_COLUMN, index=e.index))
         elif isinstance(e, _Lit):
             out.append(dict(op=abi.EXPR_CONST, value=e.value, dtype=e.dtype))
+        elif isinstance(e, _Func):
+            emit(e.a)
+            out.append(dict(op=abi.EXPR_FUNC, index=abi.EXPR_FUNCS[e.name]))
         else:
             emit(e.a)
             emit(e.b)
@@ -176,8 +247,9 @@ def postfix(exprs: Sequence[Expr]) -> List[dict]:
 
 class ExprProgram:
     """Expressions bound to their columns, marshalled as `dbg_expr_program` (kept alive by this
-    object).  `cols` holds `dbg_column` structs or column objects (DeviceColumn): objects are kept
-    referenced here, as FilterProgram keeps its own."""
+    object).  `cols` holds `dbg_column` structs or column objects (DeviceColumn; Date, Timestamp
+    and String columns for the functions that take them): objects are kept referenced here, as
+    FilterProgram keeps its own.  The program's `reserved` word is 0: the session timezone is UTC."""
 
     def __init__(self, exprs: Sequence[Expr], cols: Sequence):
         self.exprs = list(exprs)

@@ -646,7 +646,7 @@ int dbg_agg_merge_fixed(dbg_agg_handle* h, const void* dev_bufs, int32_t n_bufs,
  * *n_sel its count (synchronous). */
 int dbg_filter_select(const dbg_filter* filter, uint64_t rows, uint32_t* sel_out, uint64_t* n_sel,
                       void* hip_stream);
-/* ---- scalar projection: plus / minus / multiply in front of the aggregate ----
+/* ---- scalar projection: plus / minus / multiply, date / time functions and length() in front of the aggregate ----
  * The seam: the projection the planner puts before an aggregate whose arguments or group keys are
  * expressions — BlockOperator::Map (src/query/sql/src/evaluator/block_operator.rs:50-80) calls
  * Evaluator::run and appends the result columns that TransformPartialAggregate then indexes.  Here
@@ -658,6 +658,7 @@ int dbg_filter_select(const dbg_filter* filter, uint64_t rows, uint32_t* sel_out
  *   DBG_EXPR_CONST    push the constant of type `dt` (not nullable): integers in i64 (unsigned: the
  *                     u64 bits), floats in f64, Decimal128 in (i128_hi:i128_lo) at dt's scale
  *   DBG_EXPR_PLUS / _MINUS / _MULTIPLY   pop b, pop a, push a op b
+ *   DBG_EXPR_FUNC     pop a, push f(a), f = the dbg_expr_func in `index` (see "Functions" below)
  *   DBG_EXPR_STORE    write the top of the stack to output `index` without popping it, so a later
  *                     operator can take the stored value (TPC-H Q1's charge reuses disc_price)
  * At the end every output 0..n_outputs-1 has been stored exactly once and every value still on the
@@ -681,17 +682,82 @@ int dbg_filter_select(const dbg_filter* filter, uint64_t rows, uint32_t* sel_out
  *    value do_round_mul (decimal.rs:465-478), an error only outside the i128 range.
  *  - NULLs (EXP/function.rs:562-571, 660-710): a result is nullable if any operand is, its validity
  *    the AND of theirs; a NULL row raises nothing and its data bytes are unspecified.
- * Refused with DBG_ERR_UNSUPPORTED and a message naming it: Decimal256, String, Boolean, Date and
- * Timestamp operands, Decimal mixed with Float, NULL constants.  Division, modulo, unary minus,
- * casts and functions have no op. */
+ * Refused with DBG_ERR_UNSUPPORTED and a message naming it: Decimal256 and Boolean operands, Date,
+ * Timestamp and String operands of plus / minus / multiply, Date, Timestamp and String constants,
+ * String results, Decimal mixed with Float, NULL constants.  Division, modulo, unary minus and
+ * casts have no op.
+ *
+ * Functions (DBG_EXPR_FUNC, `index` = a dbg_expr_func): pop one value, push one.  Date and
+ * Timestamp values are column leaves or function results; a Date, Timestamp or String value can be
+ * consumed only by a function that takes its type, or (Date, Timestamp) stored.  A number result
+ * feeds plus / minus / multiply like any other number: to_year(d) * 100 + to_month(d).  A function's
+ * result is nullable exactly when its operand is (register_passthrough_nullable_1_arg), and a NULL
+ * row raises nothing.  A function on a type it does not take, and a function id that is not
+ * defined, are DBG_ERR_INVALID.
+ *  - The session timezone is UTC, the reference's default: dbg_expr_program.reserved must be 0 and
+ *    means "session timezone UTC"; anything else is DBG_ERR_INVALID.  For UTC the reference's TzLUT
+ *    has offset_round_hour and offset_round_minute both true (EXP/utils/date_helper.rs:47-55) and no
+ *    local time falls into a DST gap, so eval_date's "cannot parse to type `Date`" cannot occur.  A
+ *    caller whose session uses another zone keeps the CPU path.
+ *  - The values are the reference's arithmetic as written: to_timestamp floors a negative
+ *    microsecond count (date_helper.rs:256-265), so every civil field before the epoch comes from
+ *    the floored second; to_start_of_second is us / 10^6 * 10^6 truncating; the other sub-day
+ *    rounders are us / d * d for us > 0 and (us + 10^6 - d) / d * d, truncating, otherwise
+ *    (:159-187); to_start_of_day is the floored civil date at 00:00:00.
+ *  - Valid inputs are the reference's ranges, Date -354285..2932896 and Timestamp
+ *    -30610224000000000..253402300799999999.  A value outside them is the caller's breach: the
+ *    result of that row is unspecified, nothing is raised and nothing but that row is written.
+ *  - length(String) is the number of bytes b with (b & 0xC0) != 0x80: val.chars().count() for every
+ *    valid UTF-8 string; invalid bytes are counted the same way and raise nothing. */
 typedef enum {
     DBG_EXPR_COLUMN = 0,
     DBG_EXPR_CONST = 1,
     DBG_EXPR_PLUS = 2,
     DBG_EXPR_MINUS = 3,
     DBG_EXPR_MULTIPLY = 4,
-    DBG_EXPR_STORE = 5
+    DBG_EXPR_STORE = 5,
+    DBG_EXPR_FUNC = 6
 } dbg_expr_op;
+
+/* Function ids (0 is not a function).  D = Date, T = Timestamp operand.
+ * register_to_number_functions (FUNCS/datetime.rs:1098-1388), values from ToNumber
+ * (EXP/utils/date_helper.rs:402-516) and TzLUT::to_hour / to_minute / to_second (:210-239): */
+typedef enum {
+    DBG_FUNC_TO_YYYYMM = 1,          /* D, T -> UInt32   year * 100 + month */
+    DBG_FUNC_TO_YYYYMMDD = 2,        /* D, T -> UInt32 */
+    DBG_FUNC_TO_YYYYMMDDHH = 3,      /* D, T -> UInt64   (a Date is its midnight) */
+    DBG_FUNC_TO_YYYYMMDDHHMMSS = 4,  /* D, T -> UInt64 */
+    DBG_FUNC_TO_YEAR = 5,            /* D, T -> UInt16 */
+    DBG_FUNC_TO_QUARTER = 6,         /* D, T -> UInt8 */
+    DBG_FUNC_TO_MONTH = 7,           /* D, T -> UInt8 */
+    DBG_FUNC_TO_DAY_OF_MONTH = 8,    /* D, T -> UInt8 */
+    DBG_FUNC_TO_DAY_OF_WEEK = 9,     /* D, T -> UInt8    Monday = 1 */
+    DBG_FUNC_TO_DAY_OF_YEAR = 10,    /* D, T -> UInt16 */
+    DBG_FUNC_TO_WEEK_OF_YEAR = 11,   /* D, T -> UInt32   ISO week */
+    DBG_FUNC_TO_UNIX_TIMESTAMP = 12, /* T -> Int64       the floored second */
+    DBG_FUNC_TO_HOUR = 13,           /* T -> UInt8 */
+    DBG_FUNC_TO_MINUTE = 14,         /* T -> UInt8 */
+    DBG_FUNC_TO_SECOND = 15,         /* T -> UInt8 */
+    /* register_rounder_functions (FUNCS/datetime.rs:1611-1862): TzLUT::round_us
+     * (date_helper.rs:147-208), T -> Timestamp */
+    DBG_FUNC_TO_START_OF_SECOND = 16,
+    DBG_FUNC_TO_START_OF_MINUTE = 17,
+    DBG_FUNC_TO_START_OF_FIVE_MINUTES = 18,
+    DBG_FUNC_TO_START_OF_TEN_MINUTES = 19,
+    DBG_FUNC_TO_START_OF_FIFTEEN_MINUTES = 20,
+    DBG_FUNC_TIME_SLOT = 21,         /* thirty minutes */
+    DBG_FUNC_TO_START_OF_HOUR = 22,
+    DBG_FUNC_TO_START_OF_DAY = 23,
+    /* ... and DateRounder (date_helper.rs:530-619), D, T -> Date */
+    DBG_FUNC_TO_MONDAY = 24,         /* also to_start_of_week(x, 1) */
+    DBG_FUNC_TO_START_OF_WEEK = 25,  /* mode 0: the last Sunday */
+    DBG_FUNC_TO_START_OF_MONTH = 26,
+    DBG_FUNC_TO_START_OF_QUARTER = 27,
+    DBG_FUNC_TO_START_OF_YEAR = 28,
+    DBG_FUNC_TO_START_OF_ISO_YEAR = 29,
+    /* length(String) -> UInt64: val.chars().count() (FUNCS/string.rs:166-170) */
+    DBG_FUNC_LENGTH = 30
+} dbg_expr_func;
 
 #define DBG_EXPR_MAX_NODES 64
 #define DBG_EXPR_MAX_COLUMNS 16
@@ -699,7 +765,7 @@ typedef enum {
 
 typedef struct dbg_expr_node {
     int32_t op;      /* dbg_expr_op */
-    int32_t index;   /* COLUMN: index into dbg_expr_program.cols; STORE: output */
+    int32_t index;   /* COLUMN: index into dbg_expr_program.cols; STORE: output; FUNC: dbg_expr_func */
     dbg_datatype dt; /* CONST */
     int64_t i64;
     double f64;
@@ -713,7 +779,7 @@ typedef struct dbg_expr_program {
     int32_t n_cols;
     const dbg_column* cols;
     int32_t n_outputs;
-    int32_t reserved;
+    int32_t reserved; /* must be 0: the session timezone is UTC */
 } dbg_expr_program;
 
 /* The type of output k: the one place expression types are decided (as dbg_agg_result_type is for
